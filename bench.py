@@ -2,7 +2,7 @@
 """Throughput benchmark of the hot path: env-steps/s of the batched Spark-scheduling simulator.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs B] [--config c2|c3] [--policy hash|fair]
-                    [--mode step|fused] [--no-cpu-baseline] [--no-c3] [--no-decima] [--sustained-s S]
+                    [--mode step|fused] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-c3] [--no-decima] [--sustained-s S]]
 
 A "step" is ONE batched step of all envs of a rank: on-device policy kernel + step kernel
 (`--mode step`, the drop-in boundary: sss_policy + sss_step per step), or one iteration of the
@@ -21,11 +21,17 @@ returns after the timed region (the stand-in for the reference's Pipe gather,
 trainers/trainer.py:113-121). Weak scaling.
 
 Prints ONE JSON line on rank 0 (see the driver contract) including `roofline` (SURVEY 8(d) model
-bytes of the dominant kernel / its HIP-event-measured duration / 8 TB/s), `cpu_baseline` (the C
-oracle, oracle/sss_oracle.c, timed on this box's host on a bounded sample), `step_tail` (how much
-of a step launch is the wait for its slowest env), `sustained` (the same mode over about a second
-of stepping when the K timed steps are shorter than that) and, at N = 1, a `c3` record with the same
-measurements on BASELINE config 3 (4096 envs, 50 executors, 200 jobs, fair policy).
+bytes of the dominant kernel / its HIP-event-measured duration / 8 TB/s). A plain run does only what
+that line needs: set-up, W warm-up steps, the K timed steps, the line. `--full` adds everything else
+the benchmark measures: `cpu_baseline` (the C oracle, oracle/sss_oracle.c, timed on this box's host
+on a bounded sample), `step_tail` (how much of a step launch is the wait for its slowest env),
+`sustained` (the same mode over about a second of stepping when the K timed steps are shorter than
+that), the other mode, launches with an event budget and, at N = 1, records on BASELINE config 3
+(4096 envs, 50 executors, 200 jobs, fair policy), on 100 executors, on the 'deep' trace regime, with
+Decima in the loop and of one PPO iteration; the --no-* options skip single records of it.
+
+`--dump-outputs DIR`: after the timed steps, what the last of them handed its caller (rank 0's
+envs; dump_outputs) as DIR/<name>.npy. The inputs are seeded: the same arguments give the same outputs.
 """
 from __future__ import annotations
 
@@ -604,6 +610,47 @@ def deep_record(args, B: int, dev, rank: int, world: int) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(bench: "Bench", mode: str, out_dir: str) -> dict:
+    """what the last timed step handed its caller, this rank's envs in env order, as out_dir/<name>.npy: the observation (`nodes`,
+    `edge_links`, `dag_ptr`, `exec_supplies`, `obs_i32` - the OBS_FIELDS), `obs_f64` (reward, wall time) and, in step mode, the
+    actions the on-device policy returned for that step (`stage_idx`, `num_exec`). Rows past an env's n_nodes / n_edges / n_jobs are
+    padding a caller does not read: written as zeros. Node features in float32, everything else in float64 (exact for the i32
+    fields). Past DUMP_LIMIT_BYTES in all, a fixed sample of envs (numpy seed 0) is written, and `env_index` names them."""
+    import numpy as np
+
+    torch = bench.torch
+    torch.cuda.synchronize()
+    cat = lambda name: torch.cat([getattr(e, name) for e in bench.shards])  # noqa: E731
+    obs_i32 = cat("obs_i32")
+    B = obs_i32.shape[0]
+    n_nodes, n_edges, n_jobs = (obs_i32[:, k].long()[:, None] for k in range(3))
+
+    def valid(t, n):
+        keep = torch.arange(t.shape[1], device=t.device)[None, :] < n
+        return torch.where(keep.view(keep.shape + (1,) * (t.dim() - 2)), t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+    outs = {"nodes": (valid(cat("nodes"), n_nodes), np.float32), "edge_links": (valid(cat("edge_links"), n_edges), np.float64),
+            "dag_ptr": (valid(cat("dag_ptr"), n_jobs + 1), np.float64), "exec_supplies": (valid(cat("exec_supplies"), n_jobs), np.float64),
+            "obs_i32": (obs_i32, np.float64), "obs_f64": (cat("obs_f64"), np.float64)}
+    if mode == "step":
+        outs["stage_idx"], outs["num_exec"] = (cat("_act_stage"), np.float64), (cat("_act_nexec"), np.float64)
+    per_env = sum(t[0].numel() * np.dtype(dt).itemsize for t, dt in outs.values())
+    idx = None
+    if per_env * B > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(B, (DUMP_LIMIT_BYTES - 4096) // (per_env + 8), replace=False))
+        outs["env_index"] = (torch.from_numpy(idx), np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    sel = None if idx is None else torch.from_numpy(idx).to(obs_i32.device)
+    for name, (t, dt) in outs.items():
+        if sel is not None and name != "env_index":
+            t = t.index_select(0, sel)
+        np.save(osp.join(out_dir, f"{name}.npy"), t.cpu().numpy().astype(dt))
+    return {"dir": out_dir, "envs": B if idx is None else len(idx), "of_envs": B, "arrays": sorted(outs)}
+
+
 def run_ranks_myself(args) -> int:
     """--gpus N without a torch.distributed environment: N fresh rank processes (nothing here has touched the GPU)"""
     from spark_sched_sim_amd.distributed import launch_ranks
@@ -643,6 +690,11 @@ def main() -> None:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=8.0, help="seconds of the single-core CPU leg (the all-core and config-3 legs take at most half of it each)")
     ap.add_argument("--sustained-s", type=float, default=1.2, help="a second, longer timed region in the same mode when the K timed steps last less than this (0: off)")
+    ap.add_argument("--full", action="store_true", help="everything the benchmark measures besides the headline: the sustained window, the other "
+                    "mode, step tails, launches with an event budget, CPU baselines and, at N = 1 / --config c2, the config 3, 100-executor, "
+                    "'deep', Decima and PPO records (the --no-* options skip single ones). Off: set-up, warm-up, the K timed steps, the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last of them returned to its "
+                    "caller (rank 0's envs) as DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed sample of envs beyond that)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL on ROCm); 'gloo' only for plumbing tests")
     ap.add_argument("--device-index", type=int, default=None, help="override LOCAL_RANK -> device mapping (plumbing tests on one GPU)")
     args = ap.parse_args()
@@ -675,19 +727,21 @@ def main() -> None:
     cfg = bench.cfg
 
     primary = bench.measure(args.mode, args.steps, args.warmup)
+    dumped = dump_outputs(bench, args.mode, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     # K timed steps can be a few milliseconds (the driver runs --steps 20): the same measurement over a region of
     # about a second next to it, so that the line also carries a figure that does not depend on which 20 steps it met
-    sustained = None
-    if args.sustained_s > 0 and primary["ms_per_step"] * args.steps < 1e3 * args.sustained_s:
-        k_long = int(min(200_000, max(args.steps + 1, 1e3 * args.sustained_s / max(1e-3, primary["ms_per_step"]))))
-        long_run = bench.measure(args.mode, k_long, 0)
-        sustained = {"value": long_run["value"], "unit": "env-steps/s", "steps": k_long, "ms_per_step": long_run["ms_per_step"], "mode": args.mode,
-                     "events_per_step": long_run["events_per_step"], "roofline": long_run["roofline"],
-                     "what": f"same mode, same envs, {k_long} timed batched steps right after the K = {args.steps} of `value`"}
+    sustained = secondary = tail = bounded = None
     other_mode = "fused" if args.mode == "step" else "step"
-    secondary = None if args.single_mode else bench.measure(other_mode, args.steps, args.warmup)
-    tail = bench.step_tail() if (world == 1 and args.shards == 1) else None
-    bounded = bounded_record(bench, args, args.config, args.steps, args.warmup) if world == 1 else None
+    if args.full:
+        if args.sustained_s > 0 and primary["ms_per_step"] * args.steps < 1e3 * args.sustained_s:
+            k_long = int(min(200_000, max(args.steps + 1, 1e3 * args.sustained_s / max(1e-3, primary["ms_per_step"]))))
+            long_run = bench.measure(args.mode, k_long, 0)
+            sustained = {"value": long_run["value"], "unit": "env-steps/s", "steps": k_long, "ms_per_step": long_run["ms_per_step"], "mode": args.mode,
+                         "events_per_step": long_run["events_per_step"], "roofline": long_run["roofline"],
+                         "what": f"same mode, same envs, {k_long} timed batched steps right after the K = {args.steps} of `value`"}
+        secondary = None if args.single_mode else bench.measure(other_mode, args.steps, args.warmup)
+        tail = bench.step_tail() if (world == 1 and args.shards == 1) else None
+        bounded = bounded_record(bench, args, args.config, args.steps, args.warmup) if world == 1 else None
 
     if world > 1:
         # the one exchange of the path: all-gather of per-env episode summaries (RCCL)
@@ -745,7 +799,9 @@ def main() -> None:
             out["other_mode"] = dict(secondary, mode=other_mode)
         if bounded is not None:
             out["bounded_launches"] = bounded
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, policy, args.cpu_budget, args.pack)
             try:
                 out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(cfg, policy, min(4.0, args.cpu_budget / 2), args.pack)
@@ -759,9 +815,9 @@ def main() -> None:
     del bench  # (the env's arenas are torch tensors: dropped with the last reference, not by close())
 
     # BASELINE config 3 next to the headline (N = 1): same measurements, its own roofline and CPU baseline
-    if world == 1 and args.config == "c2" and not args.no_deep and args.shards == 1 and args.pack == "default":
+    if args.full and world == 1 and args.config == "c2" and not args.no_deep and args.shards == 1 and args.pack == "default":
         out["deep"] = deep_record(args, B, dev, rank, world)
-    if world == 1 and args.config == "c2" and not args.no_c3 and args.shards == 1:
+    if args.full and world == 1 and args.config == "c2" and not args.no_c3 and args.shards == 1:
         try:
             b3 = Bench(args, "c3", DEFAULT_POLICY["c3"], B, dev, rank, world)
             k3, w3 = max(10, min(args.steps, 300)), max(5, min(args.warmup, 50))
@@ -796,7 +852,7 @@ def main() -> None:
             out["c3"] = {"error": repr(e)}
     # more than 64 executors (the wide instantiation of the kernels, csrc/sss_hip_wide.hip) next to the headline (N = 1): 100 executors,
     # 200 jobs, step mode at 1024 and at 4096 envs, with the C oracle on all host cores beside it
-    if world == 1 and args.config == "c2" and not args.no_e100 and args.shards == 1:
+    if args.full and world == 1 and args.config == "c2" and not args.no_e100 and args.shards == 1:
         try:
             rec = {"what": "100 executors, 200 TPC-H-format jobs (job_arrival_rate 8e-05/ms), on-device 'fair' policy, auto-reset, steady state; step mode "
                            "(sss_policy + sss_step per batched step); the wide instantiation: two executors per lane"}
@@ -816,7 +872,7 @@ def main() -> None:
         except Exception as e:
             out["e100"] = {"error": repr(e)}
     if rank == 0:
-        if world == 1 and not args.no_decima and args.config == "c2":
+        if args.full and world == 1 and not args.no_decima and args.config == "c2":
             try:  # SURVEY 8(f) next-1 on the same env sizing; never let it take the bench line down
                 out["decima_in_loop"] = decima_in_loop(cfg, B, dev, pack)
             except Exception as e:
@@ -825,7 +881,7 @@ def main() -> None:
                 out["decima_in_loop_1024"] = decima_in_loop(cfg, 1024, dev, pack)
             except Exception as e:
                 out["decima_in_loop_1024"] = {"error": repr(e)}
-        if world == 1 and not args.no_ppo and args.config == "c2":
+        if args.full and world == 1 and not args.no_ppo and args.config == "c2":
             try:  # SURVEY 8(f) next-3 / BASELINE config 5 at one rank's share; never let it take the bench line down
                 out["ppo_config5_share"] = ppo_config5_share(dev)
             except Exception as e:

@@ -217,20 +217,23 @@ def test_large_node_capacity_falls_back_to_tensor_op_graph():
     env.close()
 
 
-def test_reference_checkpoint_loads_unchanged():
-    """`models/decima/model.pt` of the reference (present in the build container only): every key
+def test_reference_checkpoint_loads_unchanged(tmp_path):
+    """`models/decima/model.pt` of the reference (its tensors, in their order, stored as
+    tests/golden/decima_reference_model.npz and saved back as a torch checkpoint here): every key
     and shape of its state dict matches `DecimaPolicy`, strictly"""
+    import collections
     import os.path as osp
 
-    import pytest
+    import numpy as np
     import torch
 
     from decima_util import AGENT
+    from golden_util import GOLDEN_DIR
     from spark_sched_sim_amd.decima import DecimaPolicy
 
-    path = "/root/reference/models/decima/model.pt"
-    if not osp.exists(path):
-        pytest.skip("reference checkpoint not available here")
+    z = np.load(osp.join(GOLDEN_DIR, "decima_reference_model.npz"))
+    path = str(tmp_path / "model.pt")
+    torch.save(collections.OrderedDict((k, torch.from_numpy(z[k])) for k in z.files), path)
     policy = DecimaPolicy(num_executors=50, **AGENT, state_dict_path=path)
     sd = torch.load(path, map_location="cpu")
     assert set(sd) == set(policy.state_dict()) and sum(v.numel() for v in sd.values()) == 20802
