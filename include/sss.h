@@ -114,7 +114,11 @@ int sss_step_bounded(sss_handle* h, const int32_t* stage_idx_dev, const int32_t*
 /* On-device counterparts of the reference's heuristic Scheduler plugins; they fill one action per
  * env for the next sss_step. policy: 0 = fair (RoundRobinScheduler(dynamic_partition=True),
  * schedulers/heuristics/round_robin.py:7-49), 1 = FIFO (dynamic_partition=False), 2 = the build's
- * counter-based uniform-random policy (param = per-mille probability of stage_idx = -1). */
+ * counter-based uniform-random policy (param = per-mille probability of stage_idx = -1), 3 = weighted
+ * fair (the Decima paper's baseline: per-job executor caps in proportion to job work^alpha; param = alpha,
+ * an integer in [-4, 4], anything else fails with -23), 4 = SJF-CP (shortest job first, inside it the
+ * schedulable stage at the head of the critical path; param unused). 3 and 4 are defined on the observation
+ * and match the host plugins WeightedFairScheduler / SJFCPScheduler (schedulers.py) bit for bit. */
 int sss_policy(sss_handle* h, int policy, int param, int32_t* stage_idx_dev, int32_t* num_exec_dev, void* stream);
 
 /* n_steps x (policy -> step -> observe) per env in ONE launch: the episode loop of reference

@@ -30,7 +30,10 @@ int sss_narrow_launch_policy(const SssKernelArgs& a, int num_envs, int policy, i
   return (int)hipGetLastError();
 }
 int sss_narrow_launch_rollout(const SssKernelArgs& a, int num_envs, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride, void* stream) {
-  hipLaunchKernelGGL(sss_rollout_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, n_steps, auto_reset, seed_stride);
+  if (policy >= SSS_POLICY_WFAIR)  // weighted fair / SJF-CP: the kernel that has them (sss_sim.h)
+    hipLaunchKernelGGL(sss_rollout_heur_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, n_steps, auto_reset, seed_stride);
+  else
+    hipLaunchKernelGGL(sss_rollout_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, n_steps, auto_reset, seed_stride);
   return (int)hipGetLastError();
 }
 

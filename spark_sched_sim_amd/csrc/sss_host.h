@@ -481,11 +481,18 @@ extern "C" int sss_step_bounded(sss_handle* h, const int32_t* stage_idx_dev, con
   return 0;
 }
 
+// policy ids of sss_policy / sss_rollout (include/sss.h); weighted fair (3) takes its exponent alpha in [-4, 4] as `param`
+static int sss_check_policy(int policy, int param) {
+  if (policy < 0 || policy > 4) return sss_fail(-23, "unknown policy");
+  if (policy == 3 && (param < -4 || param > 4)) return sss_fail(-23, "weighted fair: alpha (param) must be in [-4, 4], got " + std::to_string(param));
+  return 0;
+}
+
 extern "C" int sss_policy(sss_handle* h, int policy, int param, int32_t* stage_idx_dev, int32_t* num_exec_dev, void* stream) {
   if (!h || !stage_idx_dev || !num_exec_dev) return sss_fail(-1, "NULL argument");
   if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
   BeDeviceGuard guard(h->device);
-  if (policy < 0 || policy > 2) return sss_fail(-23, "unknown policy");
+  if (int rc = sss_check_policy(policy, param)) return rc;
   const SssKernelArgs ka = sss_args(h);
   if (int rc = sss_is_wide(h->L.E) ? sss_wide_launch_policy(ka, h->L.num_envs, policy, param, stage_idx_dev, num_exec_dev, stream)
                                    : be_launch_policy(ka, h->L.num_envs, policy, param, stage_idx_dev, num_exec_dev, stream)) return sss_fail(-30, std::string("policy launch failed: ") + be_error(rc));
@@ -496,7 +503,7 @@ extern "C" int sss_rollout(sss_handle* h, int policy, int param, int n_steps, in
   if (!h) return sss_fail(-1, "NULL argument");
   if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
   BeDeviceGuard guard(h->device);
-  if (policy < 0 || policy > 2) return sss_fail(-23, "unknown policy");
+  if (int rc = sss_check_policy(policy, param)) return rc;
   if (n_steps < 0) return sss_fail(-24, "n_steps must be >= 0");
   const SssKernelArgs ka = sss_args(h);
   if (int rc = sss_is_wide(h->L.E) ? sss_wide_launch_rollout(ka, h->L.num_envs, policy, param, n_steps, auto_reset, seed_stride, stream)

@@ -402,6 +402,22 @@ SSS_DEV int obs_num_committable() {
   return (int)g_c.pool_hdr[p].used - (int)g_c.pool_hdr[p].commit_from;
 }
 
+// find_stage of one job: its first schedulable stage with no active parent, else its first schedulable stage, else -1
+SSS_DEV int find_stage_dev(uint64_t sm, uint64_t act, int gs) {
+  int best = -1;
+  uint64_t m = sm;
+  while (m) {
+    int s = ctz64(m);
+    m &= m - 1;
+    if ((g_c.pk.stage_parent_mask[gs + s] & act) == 0) {
+      best = s;
+      break;
+    }
+  }
+  if (best < 0 && sm) best = ctz64(sm);
+  return best;
+}
+
 // RoundRobinScheduler.schedule (reference schedulers/heuristics/round_robin.py:14-49 with
 // find_stage / preprocess_obs of heuristics/utils.py:5-37). All lanes; results are uniform.
 SSS_DEV void policy_fair(bool dynamic_partition, int& stage_idx, int& num_exec) {
@@ -427,18 +443,7 @@ SSS_DEV void policy_fair(bool dynamic_partition, int& stage_idx, int& num_exec) 
       const SssJob& job = (*jobp(j));
       sm = job.sched_mask, act = job.active_mask, sup = job.supply, gs = job.gs_base;
     }
-    // find_stage: first schedulable stage with no active parent, else first schedulable stage
-    int best = -1;
-    uint64_t m = sm;
-    while (m) {
-      int s = ctz64(m);
-      m &= m - 1;
-      if ((g_c.pk.stage_parent_mask[gs + s] & act) == 0) {
-        best = s;
-        break;
-      }
-    }
-    if (best < 0 && sm) best = ctz64(sm);
+    int best = find_stage_dev(sm, act, gs);
     uint32_t cnt = (uint32_t)popc64(sm);
     uint32_t excl = wave_scan_excl_u32(cnt);
     uint32_t total = wave_sum_u32(cnt);
@@ -461,6 +466,172 @@ SSS_DEV void policy_fair(bool dynamic_partition, int& stage_idx, int& num_exec) 
     stage_idx = first_rank, num_exec = ncommit < room ? ncommit : room;
   } else {
     stage_idx = -1, num_exec = ncommit;
+  }
+  if (num_exec < 1) num_exec = 1;
+}
+
+// ---- weighted fair and SJF-CP: the stronger heuristics of the Decima paper (Mao et al., SIGCOMM 2019, 7.2) ----
+// Both are defined on the observation (schedulers.py WeightedFairScheduler / SJFCPScheduler), and must agree with
+// those host plugins bit for bit. work(n) = f64(nodes[n,0]) * f64(nodes[n,1]) = (double)(float)remaining * (double)duration is
+// one exact product of two f32 values, so only the order of the sums is fixed: a job's work W_j is summed from 0.0 over its
+// active stages in ascending stage id (the order of its node rows), the weighted-fair total S over the active jobs in active
+// order. f64 adds and multiplies only (the unit builds with -ffp-contract=off), no pow.
+
+SSS_DEV double stage_work(const JobView& v, int s) { return (double)(float)v.st[s].remaining * (double)v.dur[s]; }
+
+SSS_DEV double job_work(const JobView& v, uint64_t act) {
+  double w = 0.0;
+  for (uint64_t m = act; m; m &= m - 1) w += stage_work(v, ctz64(m));
+  return w;
+}
+
+// w_j = max(W_j, 1)^alpha by repeated multiplication (host and device pow differ in the last ulp), alpha in [-4, 4]
+SSS_DEV double wfair_weight(double W, int alpha) {
+  if (alpha == 0) return 1.0;
+  const double x = W > 1.0 ? W : 1.0;
+  const int k = alpha < 0 ? -alpha : alpha;
+  double p = x;
+  for (int i = 1; i < k; i++) p *= x;
+  return alpha > 0 ? p : 1.0 / p;
+}
+
+// weighted fair: RoundRobinScheduler's structure with the per-job cap min(E, max(1, ceil(E * w_j / S))) in place of
+// ceil(E / A). All lanes; results are uniform.
+SSS_DEV void policy_wfair(int alpha, int& stage_idx, int& num_exec) {
+  int lane = wave_lane();
+  int A = g_hot.h.n_active;
+  uint32_t srck = g_hot.h.curr_source;
+  int ncommit = obs_num_committable();
+  int src_job = (srck == POOL_NONE || srck == POOL_COMMON) ? -1 : key_job(srck);
+  const int E = g_c.E;
+  int n_chunks = (A + 63) / 64;
+  if (n_chunks == 0) n_chunks = 1;
+  // pass 1 - lanes over jobs: the weights; S summed left to right by wave-uniform lane reads (no LDS array)
+  double S = 0.0, w_last = 1.0;
+  for (int ch = 0; ch < n_chunks; ch++) {
+    int k = ch * 64 + lane;
+    double w = 1.0;
+    if (k < A) {
+      const JobView v = jobview(lds_active()[k]);
+      w = wfair_weight(job_work(v, v.job->active_mask), alpha);
+    }
+    int n = A - ch * 64 < 64 ? A - ch * 64 : 64;
+    for (int l = 0; l < n; l++) S += wave_readlane_f64(w, l);
+    w_last = w;
+  }
+  // pass 2 - find_stage per job, the caps, the first eligible job (as policy_fair); one chunk keeps its weights in registers
+  int src_rank = -1, first_rank = -1, first_sup = 0, first_cap = 0;
+  uint32_t base = 0;
+  for (int ch = 0; ch < n_chunks; ch++) {
+    int k = ch * 64 + lane;
+    bool valid = k < A;
+    int j = valid ? (int)lds_active()[k] : 0;
+    uint64_t sm = 0, act = 0;
+    int sup = 0, gs = 0, cap = 0;
+    if (valid) {
+      const JobView v = jobview(j);
+      sm = v.job->sched_mask, act = v.job->active_mask, sup = v.job->supply, gs = v.job->gs_base;
+      const double w = n_chunks == 1 ? w_last : wfair_weight(job_work(v, act), alpha);
+      const double c = __builtin_ceil(((double)E * w) / S);
+      cap = c < 1.0 ? 1 : (c > (double)E ? E : (int)c);
+    }
+    int best = find_stage_dev(sm, act, gs);
+    uint32_t cnt = (uint32_t)popc64(sm);
+    uint32_t excl = wave_scan_excl_u32(cnt);
+    uint32_t total = wave_sum_u32(cnt);
+    uint32_t abs_rank = base + excl + (best >= 0 ? (uint32_t)popc64(sm & (bit64(best) - 1)) : 0u);
+    bool is_src = valid && j == src_job;
+    uint64_t m_src = wave_ballot(is_src && best >= 0);
+    uint64_t m_el = wave_ballot(valid && best >= 0 && !(sup >= cap || is_src));
+    if (m_src != 0 && src_rank < 0) src_rank = (int)wave_bcast_u32(abs_rank, ctz64(m_src));
+    if (m_el != 0 && first_rank < 0) {
+      int l = ctz64(m_el);
+      first_rank = (int)wave_bcast_u32(abs_rank, l);
+      first_sup = (int)wave_bcast_u32((uint32_t)sup, l);
+      first_cap = (int)wave_bcast_u32((uint32_t)cap, l);
+    }
+    base += total;
+  }
+  if (src_rank >= 0) {
+    stage_idx = src_rank, num_exec = ncommit;
+  } else if (first_rank >= 0) {
+    int room = first_cap - first_sup;
+    stage_idx = first_rank, num_exec = ncommit < room ? ncommit : room;
+  } else {
+    stage_idx = -1, num_exec = ncommit;
+  }
+  if (num_exec < 1) num_exec = 1;
+}
+
+// SJF-CP: the job of least work W_j among those with a schedulable stage (ties: earliest active position), inside it the
+// schedulable stage at the head of the longest critical path CP(n) = work(n) + max over active children CP(c) (ties: lowest
+// stage id), all committable executors. All lanes; results are uniform.
+SSS_DEV void policy_sjfcp(int& stage_idx, int& num_exec) {
+  int lane = wave_lane();
+  int A = g_hot.h.n_active;
+  int ncommit = obs_num_committable();
+  int n_chunks = (A + 63) / 64;
+  if (n_chunks == 0) n_chunks = 1;
+  // lanes over jobs: arg-min of (W_j, position). W_j >= 0, so its bit pattern orders like its value
+  uint64_t best_key = ~0ull;
+  int best_j = -1;
+  uint32_t best_base = 0, base = 0;  // best_base: rank of the chosen job's first schedulable node among all of them
+  for (int ch = 0; ch < n_chunks; ch++) {
+    int k = ch * 64 + lane;
+    bool valid = k < A;
+    int j = valid ? (int)lds_active()[k] : 0;
+    uint64_t sm = 0;
+    double W = 0.0;
+    if (valid) {
+      const JobView v = jobview(j);
+      sm = v.job->sched_mask;
+      W = job_work(v, v.job->active_mask);
+    }
+    uint32_t cnt = (uint32_t)popc64(sm);
+    uint32_t excl = wave_scan_excl_u32(cnt);
+    uint32_t total = wave_sum_u32(cnt);
+    bool cand = valid && sm != 0;
+    uint64_t key = cand ? f64_bits(W) : ~0ull;
+    uint64_t mn = wave_min_u64(key);
+    uint64_t hit = wave_ballot(cand && key == mn);
+    if (hit != 0 && mn < best_key) {  // strictly less: an equal W in a later chunk comes later in active order
+      int l = ctz64(hit);
+      best_key = mn, best_j = (int)wave_bcast_u32((uint32_t)j, l), best_base = base + wave_bcast_u32(excl, l);
+    }
+    base += total;
+  }
+  stage_idx = -1, num_exec = ncommit;
+  if (best_j >= 0) {
+    // lanes over the chosen job's stages: CP by relaxation. Each round is a Jacobi sweep (cp of every child read from the
+    // previous round); from cp = work, a stage's value is final once the rounds reach its height, and a max is exact, so
+    // the fixed point is the same bits in any order. A DAG of at most 64 stages settles within 64 rounds.
+    const JobView v = jobview(best_j);
+    const uint64_t act = v.job->active_mask, sm = v.job->sched_mask;
+    const bool mine = (act >> lane) & 1;
+    const double w = mine ? stage_work(v, lane) : 0.0;
+    const uint64_t kids = mine ? g_c.pk.stage_child_mask[v.job->gs_base + lane] & act : 0;
+    double cp = w;
+    for (int r = 0; r <= 64; r++) {
+      double mx = 0.0;  // CP >= 0: max(0, max over children) = max over children
+      uint64_t rem = kids;
+      while (wave_ballot(rem != 0)) {
+        const bool take = rem != 0;
+        const int c = take ? ctz64(rem) : lane;
+        rem &= rem - 1;
+        const double vc = wave_bcast_f64(cp, c);
+        if (take && vc > mx) mx = vc;
+      }
+      const double nc = kids ? w + mx : w;
+      const bool changed = wave_ballot(f64_bits(nc) != f64_bits(cp)) != 0;
+      cp = nc;
+      if (!changed) break;
+    }
+    // the schedulable stage of largest CP, lowest id on ties: arg-min of the complemented bit pattern
+    const bool cand = (sm >> lane) & 1;
+    const uint64_t key = cand ? ~f64_bits(cp) : ~0ull;
+    const uint64_t mn = wave_min_u64(key);
+    const uint64_t hit = wave_ballot(cand && key == mn);
+    if (hit != 0) stage_idx = (int)best_base + popc64(sm & (bit64(ctz64(hit)) - 1));
   }
   if (num_exec < 1) num_exec = 1;
 }
@@ -490,12 +661,19 @@ SSS_DEV void policy_hash(int p_none_permille, int& stage_idx, int& num_exec) {
   num_exec = 1 + (int)(h2 % (uint64_t)(ncommit > 0 ? ncommit : 1));
 }
 
-enum { SSS_POLICY_FAIR = 0, SSS_POLICY_FIFO = 1, SSS_POLICY_HASH = 2 };
+enum { SSS_POLICY_FAIR = 0, SSS_POLICY_FIFO = 1, SSS_POLICY_HASH = 2, SSS_POLICY_WFAIR = 3, SSS_POLICY_SJFCP = 4 };
 
+// kHeuristics: with weighted fair / SJF-CP (ids 3, 4). Without them the code is fair / FIFO / hash only, so that the rollout
+// kernel those run in keeps its register allocation (see sss_rollout_heur_kernel)
+template <bool kHeuristics = true>
 SSS_DEV void run_policy(int policy, int param, int& stage_idx, int& num_exec) {
   PROF3(29);
   if (policy == SSS_POLICY_HASH)
     policy_hash(param, stage_idx, num_exec);
+  else if (kHeuristics && policy == SSS_POLICY_WFAIR)
+    policy_wfair(param, stage_idx, num_exec);
+  else if (kHeuristics && policy == SSS_POLICY_SJFCP)
+    policy_sjfcp(stage_idx, num_exec);
   else
     policy_fair(policy == SSS_POLICY_FAIR, stage_idx, num_exec);
 }
@@ -513,28 +691,49 @@ SSS_KERNEL void SSS_KNAME(sss_policy_kernel)(SssKernelArgs a, int policy, int pa
 
 // n_steps x (policy -> step -> observe) per env in one launch; the env's hot block and job cache
 // stay in LDS in between. Every step still writes the full observation, as the reference's step() does.
-SSS_KERNEL void SSS_KNAME(sss_rollout_kernel)(SssKernelArgs a, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride) {
-  int env = wave_env();
-  uint8_t* base = (uint8_t*)a.B.state + (size_t)env * a.L.env_stride;
-  ctx_init();
-  env_begin(base);
-  for (int it = 0; it < n_steps; it++) {
-    bool over = wave_ballot(g_hot.h.terminated || g_hot.h.need_reset) != 0;
-    double reward = 0.0;
-    if (over) {
-      if (!auto_reset || wave_ballot(g_hot.h.err != 0) != 0) break;  // failed envs stay failed
-      do_reset(a.L, g_hot.h.seed + seed_stride, g_hot.h.time_limit);
-    } else {
-      int si, ne;
-      run_policy(policy, param, si, ne);
-      reward = do_step<true>(si, ne);
-    }
-    write_observation(a.L, a.B, env, reward);
-    wave_sync();
-  }
-  env_end(base);
+// the body of the fused rollout kernels (a macro, not a function: sss_rollout_kernel keeps the code generation it had alone)
+#define ROLLOUT_BODY(kHeuristics) \
+  int env = wave_env(); \
+  uint8_t* base = (uint8_t*)a.B.state + (size_t)env * a.L.env_stride; \
+  ctx_init(); \
+  env_begin(base); \
+  for (int it = 0; it < n_steps; it++) { \
+    bool over = wave_ballot(g_hot.h.terminated || g_hot.h.need_reset) != 0; \
+    double reward = 0.0; \
+    if (over) { \
+      if (!auto_reset || wave_ballot(g_hot.h.err != 0) != 0) break; /* failed envs stay failed */ \
+      do_reset(a.L, g_hot.h.seed + seed_stride, g_hot.h.time_limit); \
+    } else { \
+      int si, ne; \
+      run_policy<kHeuristics>(policy, param, si, ne); \
+      reward = do_step<true>(si, ne); \
+    } \
+    write_observation(a.L, a.B, env, reward); \
+    wave_sync(); \
+  } \
+  env_end(base); \
   prof3_flush();
+
+// On the GPU the fused rollout is two kernels: sss_rollout_kernel for fair / FIFO / hash, sss_rollout_heur_kernel for every
+// policy (the launchers pick it for ids 3 and 4). Inlined into the one kernel, the weighted-fair / SJF-CP bodies changed its
+// register allocation and pushed the wide instantiation past its spill budget (tests/test_abi.py); apart, the existing policies
+// run the code they ran before. (A call instead of inlining is no way out: a callee cannot read the kernel-argument segment
+// that g_c is built from.) The CPU emulator has no register budget and runs every policy through sss_rollout_kernel.
+#ifdef __HIP__
+#define SSS_ROLLOUT_HEURISTICS false
+#else
+#define SSS_ROLLOUT_HEURISTICS true
+#endif
+SSS_KERNEL void SSS_KNAME(sss_rollout_kernel)(SssKernelArgs a, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride) {
+  ROLLOUT_BODY(SSS_ROLLOUT_HEURISTICS)
 }
+#ifdef __HIP__
+SSS_KERNEL void SSS_KNAME(sss_rollout_heur_kernel)(SssKernelArgs a, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride) {
+  ROLLOUT_BODY(true)
+}
+#endif
+#undef ROLLOUT_BODY
+#undef SSS_ROLLOUT_HEURISTICS
 
 #undef H
 #undef FAIL

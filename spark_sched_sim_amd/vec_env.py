@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import workload
-from .binding import ERROR_NAMES, POLICY_IDS, Binding, SssBuffers, SssCfg, SssDecimaGraph, SssDecimaLists, device_of
+from .binding import ERROR_NAMES, POLICY_IDS, WFAIR_ALPHA_RANGE, Binding, SssBuffers, SssCfg, SssDecimaGraph, SssDecimaLists, device_of
 
 OBS_FIELDS = ("n_nodes", "n_edges", "n_jobs", "n_schedulable", "num_committable_execs", "source_job_idx",
               "terminated", "err")
@@ -253,17 +253,32 @@ class VecSparkSchedSimEnv:
 
     # ---- on-device policies and fused rollouts ---------------------------------------------
 
+    @staticmethod
+    def _policy_id(policy: str, param: int) -> int:
+        pid = POLICY_IDS[policy]
+        lo, hi = WFAIR_ALPHA_RANGE
+        if policy == "wfair" and not lo <= int(param) <= hi:
+            raise ValueError(f"wfair: alpha (param) must be an integer in [{lo}, {hi}], got {param}")
+        return pid
+
     def policy_actions(self, policy: str = "fair", param: int = 0):
-        """one action per env from an on-device heuristic ("fair" / "fifo" = the reference's
-        RoundRobinScheduler with / without dynamic partitioning, "hash" = the build's counter-based
-        uniform-random policy); returns {"stage_idx", "num_exec"} device tensors (re-used buffers)."""
-        self._b.check(self._b.lib.sss_policy(self._h, POLICY_IDS[policy], int(param), self._act_stage.data_ptr(),
+        """one action per env from an on-device heuristic; returns {"stage_idx", "num_exec"} device tensors (re-used buffers).
+
+        "fair" / "fifo": the reference's RoundRobinScheduler with / without dynamic partitioning; "hash": the build's counter-based
+        uniform-random policy (param = per-mille probability of stage_idx = -1); "wfair": weighted fair, executor caps in proportion
+        to job work^alpha (param = alpha, an integer in [-4, 4]; ValueError otherwise); "sjfcp": shortest job first, inside it the
+        stage at the head of the critical path (param unused). "wfair" / "sjfcp" equal the host plugins WeightedFairScheduler /
+        SJFCPScheduler (schedulers.py) on `obs_view(i)` bit for bit."""
+        pid = self._policy_id(policy, param)
+        self._b.check(self._b.lib.sss_policy(self._h, pid, int(param), self._act_stage.data_ptr(),
                                              self._act_nexec.data_ptr(), self._stream()))
         return {"stage_idx": self._act_stage, "num_exec": self._act_nexec}
 
     def rollout(self, policy: str, n_steps: int, param: int = 0) -> None:
-        """n_steps x (policy -> step) per env inside one kernel launch (asynchronous)"""
-        self._b.check(self._b.lib.sss_rollout(self._h, POLICY_IDS[policy], int(param), int(n_steps), int(self.auto_reset),
+        """n_steps x (policy -> step) per env inside one kernel launch (asynchronous); `policy` / `param` as for
+        `policy_actions`"""
+        pid = self._policy_id(policy, param)
+        self._b.check(self._b.lib.sss_rollout(self._h, pid, int(param), int(n_steps), int(self.auto_reset),
                                               self.seed_stride, self._stream()))
 
     def decima_graph_on_device(self, active: torch.Tensor | None = None, num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict[str, Any]:
