@@ -317,6 +317,9 @@ int sss_gnn_launch(int kind, const sss_gnn_args* args, void* stream);
  * w_*_dev: the seven MLPs packed as for sss_gnn_launch. node_scratch_dev: f32[num_envs][node_cap][53],
  * job_scratch_dev: f32[num_envs][job_cap][32] (work space). Draws are Gumbel-max over a counter-based
  * uniform stream keyed by (rng_seed, rng_counter, env, candidate): pass a new rng_counter per call.
+ * The stream's 24-bit uniforms lie strictly inside (0, 1), so its Gumbel values span [-2.85, 16.64]: a candidate scored more
+ * than ~19.5 below the best is never drawn (its softmax probability is below ~3e-9) - the one way the draws differ from an
+ * exact softmax sampler.
  * Outputs per env: stage_idx / num_exec (for sss_step; stage_idx -1 when nothing is schedulable),
  * Decima's action tuple (stage_sel, job_idx, exec_sel) and its log-probability; optional dense
  * scores (stage_scores_dev f32[num_envs][node_cap], exec_scores_dev f32[num_envs][E]; -inf = masked).
@@ -350,7 +353,8 @@ int sss_decima_policy(sss_handle* h, const sss_decima_policy_args* a, void* stre
  * sss_gnn_launch pipeline, one wavefront per observation, same Gumbel-max stream as sss_decima_policy.
  * which = 0: stage draw from stage_scores_dev (f32[n_obs][n_pad], -inf = masked) -> job_gid_dev (the
  * idx0 of the EXEC launch), stage_idx / stage_sel / job_idx, lgprob, any_stage. which = 1: executor
- * count draw from exec_scores_dev (f32[n_obs][E], any E >= 1: lanes stride over the counts) -> num_exec / exec_sel, lgprob += . */
+ * count draw from exec_scores_dev (f32[n_obs][E], any E >= 1: lanes stride over the counts) -> num_exec / exec_sel, lgprob += .
+ * As in sss_decima_policy, a candidate scored more than ~19.5 below the best (probability below ~3e-9) is never drawn. */
 typedef struct sss_decima_sample_args {
   int64_t n_pad;
   int num_executors;

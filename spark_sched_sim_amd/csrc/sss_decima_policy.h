@@ -60,7 +60,9 @@ SSS_DEV float dp_gumbel(uint64_t seed, uint64_t counter, int env, uint32_t idx, 
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   z ^= z >> 31;
-  float u = ((float)(uint32_t)(z >> 40) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
+  // (0, 1): the top 24-bit value + 0.5 rounds to 2^24 in float32, i.e. u = 1 and a key of +inf - clamped to the largest float
+  // below 1. Every other value of the stream is unchanged; the Gumbel values span [-2.85, 16.64].
+  float u = fminf(((float)(uint32_t)(z >> 40) + 0.5f) * (1.0f / 16777216.0f), 0.99999994f);
   return -logf(-logf(u));
 }
 

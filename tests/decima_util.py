@@ -215,6 +215,7 @@ def _gumbel(seed, counter, env, idx, draw):
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
     z ^= z >> 31
     u = np.float32((np.float32(z >> 40) + np.float32(0.5)) * np.float32(1.0 / 16777216.0))
+    u = min(u, np.float32(1.0 - 2.0 ** -24))  # (the kernel's clamp: the top value would round to 1.0)
     return float(-np.log(-np.log(u)))
 
 
