@@ -622,12 +622,18 @@ int sss_sequence_baselines(const sss_baseline_args* a, void* stream);
  * schedulers/decima/scheduler.py:209-232, :246-283, :289-318, :337-385). `a` is the list side (row i, leading dimension ld_a
  * floats - it may be a column slice of a wider matrix), `b` / `c` the table side (row idx[i], contiguous rows of `width` floats):
  *   SSS_ROWS_GATHER       a[i] = b[idx[i]]
- *   SSS_ROWS_SCATTER_ADD  b[idx[i]] += a[i]                  (float atomics: the order of the additions into a row is not fixed)
+ *   SSS_ROWS_SCATTER_ADD  b[idx[i]] += a[i]                  (float atomics: the order of the additions into a row is not fixed;
+ *                         SSS_ROWS_ORDERED_ADD is the same sum in a fixed order)
  *   SSS_ROWS_UPDATE       b[idx[i]] = a[i] + c[idx[i]]       (idx without repeats)
  *   SSS_ROWS_TAKE         a[i] = b[idx[i]], b[idx[i]] = 0, c[idx[i]] += a[i]     (idx without repeats)
  *   SSS_ROWS_SCATTER      b[idx[i]] = a[i]                   (idx without repeats)
  *   SSS_ROWS_SEGMENT_SUM  b[s] = sum of a[i], idx[s] <= i < idx[s + 1]  (idx: n + 1 non-decreasing row offsets of the n segments;
  *                         no atomics, the additions run in row order)
+ *   SSS_ROWS_ORDERED_ADD  b[t] = (((b[t] + a[p(i0)]) + a[p(i0 + 1)]) + ...) + a[p(i1 - 1)] for every maximal run i0 .. i1 - 1 of
+ *                         equal keys t = idx[i], p(i) = perm_dev[i] (perm_dev NULL: p(i) = i). PRECONDITION: idx is NON-DECREASING
+ *                         (not checked; sort the keys stably and pass the sort's permutation as perm_dev). No atomics: one thread
+ *                         group owns a run and adds in that fixed order, so every launch gives the same bits (the deterministic
+ *                         mode's scatter-add, spark_sched_sim_amd/train_kernels.py)
  * idx entries must be valid rows of the tables (not checked). Launches on the CURRENT device's stream `stream` (no handle). */
 #define SSS_ROWS_GATHER 0
 #define SSS_ROWS_SCATTER_ADD 1
@@ -635,6 +641,7 @@ int sss_sequence_baselines(const sss_baseline_args* a, void* stream);
 #define SSS_ROWS_TAKE 3
 #define SSS_ROWS_SCATTER 4
 #define SSS_ROWS_SEGMENT_SUM 5
+#define SSS_ROWS_ORDERED_ADD 6
 typedef struct sss_rows_args {
   int64_t n;              /* rows of the list */
   int64_t ld_a;           /* floats between rows of a (>= width) */
@@ -644,6 +651,7 @@ typedef struct sss_rows_args {
   float* a_dev;
   float* b_dev;
   float* c_dev;           /* UPDATE / TAKE only */
+  const int64_t* perm_dev; /* ORDERED_ADD only: i64[n] or NULL */
 } sss_rows_args;
 int sss_rows_op(const sss_rows_args* a, void* stream);
 

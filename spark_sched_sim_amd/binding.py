@@ -122,7 +122,7 @@ class SssMlpArgs(C.Structure):  # include/sss.h sss_mlp_args
 
 class SssRowsArgs(C.Structure):  # include/sss.h sss_rows_args
     _fields_ = [("n", C.c_int64), ("ld_a", C.c_int64), ("width", C.c_int32), ("op", C.c_int32), ("idx_dev", C.c_void_p), ("a_dev", C.c_void_p), ("b_dev", C.c_void_p),
-                ("c_dev", C.c_void_p)]
+                ("c_dev", C.c_void_p), ("perm_dev", C.c_void_p)]
 
 
 class SssConcatPart(C.Structure):  # include/sss.h sss_concat_part

@@ -861,11 +861,12 @@ extern "C" int sss_bit_lists(const sss_bit_list_args* a, void* stream) {
 
 extern "C" int sss_rows_op(const sss_rows_args* a, void* stream) {
   if (!a || !a->a_dev || !a->b_dev || (a->n > 0 && !a->idx_dev)) return sss_fail(-1, "NULL argument");
-  if (a->op < 0 || a->op > 5) return sss_fail(-33, "sss_rows_op: unknown operation");
+  if (a->op < 0 || a->op > 6) return sss_fail(-33, "sss_rows_op: unknown operation");
   if (a->width < 1 || a->width > 64 || a->ld_a < a->width || a->n < 0) return sss_fail(-33, "sss_rows_op: width must be in 1..64, ld_a >= width, n >= 0");
   if ((a->op == 2 || a->op == 3) && !a->c_dev) return sss_fail(-1, "NULL argument");
   SssRowsArgs r;
   r.n = a->n, r.ld_a = a->ld_a, r.width = a->width, r.op = a->op, r.idx = a->idx_dev, r.a = a->a_dev, r.b = a->b_dev, r.c = a->c_dev;
+  r.perm = a->op == 6 ? a->perm_dev : nullptr;
   if (r.n == 0) return 0;
   if (int rc = be_launch_rows(r, stream)) return sss_fail(-30, std::string("rows launch failed: ") + be_error(rc));
   return 0;

@@ -7,18 +7,27 @@
 // One kernel family, a "list side" array `a` (row i of the list, leading dimension ld_a floats: it may be a column slice of a
 // wider matrix) and "table side" arrays `b`, `c` (row idx[i], contiguous rows of `width` floats):
 //   GATHER       a[i] = b[idx[i]]
-//   SCATTER_ADD  b[idx[i]] += a[i]                         (float atomics: the order of the additions into a row is not fixed)
+//   SCATTER_ADD  b[idx[i]] += a[i]                         (float atomics: the order of the additions into a row is not fixed;
+//                ORDERED_ADD is the same sum in a fixed order)
 //   UPDATE       b[idx[i]] = a[i] + c[idx[i]]              (idx without repeats: the receivers of a DAG layer, forward)
 //   TAKE         a[i] = b[idx[i]], b[idx[i]] = 0, c[idx[i]] += a[i]    (idx without repeats: the same, backward)
 //   SCATTER      b[idx[i]] = a[i]                          (idx without repeats)
 //   SEGMENT_SUM  b[s] = sum of a[i] for idx[s] <= i < idx[s + 1]     (idx: n + 1 row offsets of n segments - the sums over the rows
 //                of a job, the jobs of an observation, the edges of a receiving node: no atomics, a fixed order)
+//   ORDERED_ADD  b[t] = ((b[t] + a[p(i0)]) + a[p(i0 + 1)]) + ... + a[p(i1 - 1)] for every maximal run i0 .. i1 - 1 of equal keys
+//                t = idx[i] (idx NON-DECREASING; p(i) = perm[i], or i when perm is NULL): the deterministic mode's scatter-add. The
+//                first row of a run walks it, one column per lane: each column is a sequential sum, no atomics, whatever the lane width
 // A row is handled by 2^k adjacent lanes, 16 bytes per lane when width, ld_a and the pointers allow it and 4 bytes otherwise;
 // a thread has four rows in flight. Bound: HBM (8 bytes of index + 2..3 x 4 x width bytes per row).
 #pragma once
 #include <stdint.h>
+#if defined(__HIPCC__)
+#define SSS_ROWS_FN __host__ __device__ inline
+#else
+#define SSS_ROWS_FN static inline
+#endif
 
-enum { ROWS_GATHER = 0, ROWS_SCATTER_ADD = 1, ROWS_UPDATE = 2, ROWS_TAKE = 3, ROWS_SCATTER = 4, ROWS_SEGMENT_SUM = 5 };
+enum { ROWS_GATHER = 0, ROWS_SCATTER_ADD = 1, ROWS_UPDATE = 2, ROWS_TAKE = 3, ROWS_SCATTER = 4, ROWS_SEGMENT_SUM = 5, ROWS_ORDERED_ADD = 6 };
 
 struct SssRowsArgs {
   int64_t n;        // rows of the list
@@ -29,7 +38,16 @@ struct SssRowsArgs {
   float* a;
   float* b;
   float* c;
+  const int64_t* perm;  // ORDERED_ADD: i64[n] list row of the i-th key, or NULL (the identity)
 };
+
+// ORDERED_ADD: the end of the run of equal keys that starts at row i0 (never reads idx[n])
+SSS_ROWS_FN int64_t sss_rows_run_end(const SssRowsArgs& r, int64_t i0) {
+  const int64_t key = r.idx[i0];
+  int64_t k = i0 + 1;
+  while (k < r.n && r.idx[k] == key) k++;
+  return k;
+}
 
 // one element (row i, column j) of an operation: the host backend's loop body and the statement the kernel vectorises
 template <class AddFn>
@@ -38,6 +56,15 @@ static inline void sss_rows_element(const SssRowsArgs& r, int64_t i, int j, AddF
     float v = 0.0f;
     for (int64_t k = r.idx[i]; k < r.idx[i + 1]; k++) v += r.a[k * r.ld_a + j];
     r.b[i * (int64_t)r.width + j] = v;
+    return;
+  }
+  if (r.op == ROWS_ORDERED_ADD) {  // (only the run's first row works)
+    if (i > 0 && r.idx[i - 1] == r.idx[i]) return;
+    const int64_t k1 = sss_rows_run_end(r, i);
+    float* t = r.b + r.idx[i] * (int64_t)r.width + j;
+    float v = *t;
+    for (int64_t k = i; k < k1; k++) v += r.a[(r.perm ? r.perm[k] : k) * r.ld_a + j];
+    *t = v;
     return;
   }
   const int64_t t = r.idx[i] * (int64_t)r.width + j, l = i * r.ld_a + j;
@@ -147,6 +174,17 @@ __global__ __launch_bounds__(256) void sss_rows_kernel(SssRowsArgs r, int lanes_
       }
       continue;
     }
+    if (OP == ROWS_ORDERED_ADD) {  // (tab: the key's table row; the lanes of a run's first row walk the run, the others are done)
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        if (!ok[u] || (row[u] > 0 && r.idx[row[u] - 1] == r.idx[row[u]])) continue;
+        const int64_t k1 = sss_rows_run_end(r, row[u]);
+        T acc = *(const T*)(r.b + tab[u]);
+        for (int64_t k = row[u]; k < k1; k++) acc += *(const T*)(r.a + (r.perm ? r.perm[k] : k) * r.ld_a + col[u]);
+        *(T*)(r.b + tab[u]) = acc;
+      }
+      continue;
+    }
 #pragma unroll
     for (int u = 0; u < U; u++) {
       v[u] = w[u] = SssRowsVec<VEC>::zero();
@@ -234,6 +272,7 @@ static void sss_rows_launch_op(const SssRowsArgs& r, int lanes_log, dim3 grid, h
     case ROWS_UPDATE: hipLaunchKernelGGL((sss_rows_kernel<VEC, ROWS_UPDATE>), grid, dim3(256), 0, st, r, lanes_log); break;
     case ROWS_SCATTER: hipLaunchKernelGGL((sss_rows_kernel<VEC, ROWS_SCATTER>), grid, dim3(256), 0, st, r, lanes_log); break;
     case ROWS_SEGMENT_SUM: hipLaunchKernelGGL((sss_rows_kernel<VEC, ROWS_SEGMENT_SUM>), grid, dim3(256), 0, st, r, lanes_log); break;
+    case ROWS_ORDERED_ADD: hipLaunchKernelGGL((sss_rows_kernel<VEC, ROWS_ORDERED_ADD>), grid, dim3(256), 0, st, r, lanes_log); break;
     default: hipLaunchKernelGGL((sss_rows_kernel<VEC, ROWS_TAKE>), grid, dim3(256), 0, st, r, lanes_log); break;
   }
 }

@@ -881,7 +881,8 @@ class DecimaPolicy(nn.Module):
         """scores of the schedulable stages only (scheduler.py:289-318): (f32[S], global node ids i64[S])"""
         from .train_kernels import concat_rows
         idx = g["stage_mask"].nonzero(as_tuple=True)[0]
-        inp = concat_rows([(g["x"], idx), (h["node"], idx), (h["dag"], g["node_job"][idx]), (h["glob"], g["node_obs"][idx])])
+        # (every index is non-decreasing: idx ascends, an observation's nodes are stored job by job - the deterministic backward needs no sort)
+        inp = concat_rows([(g["x"], idx), (h["node"], idx), (h["dag"], g["node_job"][idx]), (h["glob"], g["node_obs"][idx])], sorted_idx=True)
         return self.stage_policy_network.mlp_score(inp).squeeze(-1), idx
 
     def exec_scores(self, g: dict[str, Any], h: dict[str, torch.Tensor], job_gid: torch.Tensor) -> torch.Tensor:
@@ -907,7 +908,7 @@ class DecimaPolicy(nn.Module):
         total = int(caps.sum())  # (device -> host: the number of rows)
         owner = torch.repeat_interleave(torch.arange(k, device=dev), caps, output_size=total)
         count = torch.arange(total, device=dev) - (torch.cumsum(caps, 0) - caps)[owner]
-        inp = concat_rows([(base, owner), (acts[:, None], count)])
+        inp = concat_rows([(base, owner), (acts[:, None], count)], sorted_idx=(True, False))  # (owner: job after job)
         return self.exec_policy_network.mlp_score(inp).squeeze(-1), owner, count, caps
 
     @torch.no_grad()

@@ -90,12 +90,42 @@ class KernelLinear(nn.Linear):
         return F.linear(x, self.weight, self.bias)
 
 
-ROWS_GATHER, ROWS_SCATTER_ADD, ROWS_UPDATE, ROWS_TAKE, ROWS_SCATTER, ROWS_SEGMENT_SUM = 0, 1, 2, 3, 4, 5  # include/sss.h SSS_ROWS_*
+ROWS_GATHER, ROWS_SCATTER_ADD, ROWS_UPDATE, ROWS_TAKE, ROWS_SCATTER, ROWS_SEGMENT_SUM, ROWS_ORDERED_ADD = 0, 1, 2, 3, 4, 5, 6  # include/sss.h SSS_ROWS_*
 
 
-def rows_op(op: int, idx: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor | None = None, binding=None) -> None:
+def deterministic_enabled() -> bool:
+    """whether the caller asked torch for deterministic algorithms (`torch.use_deterministic_algorithms(True)`, warn-only mode
+    included): the autograd functions below then add rows with `ROWS_ORDERED_ADD` in a fixed order instead of with float atomics.
+    Read at every call, never cached."""
+    return torch.are_deterministic_algorithms_enabled()
+
+
+def sort_plan(idx: torch.Tensor):
+    """(keys, perm) of a stable sort of the i64 row ids `idx`: keys = idx[perm] non-decreasing, perm ascending within a run of
+    equal keys - the arguments of `ROWS_ORDERED_ADD` that add the rows of every key in their list order"""
+    keys, perm = torch.sort(idx, stable=True)
+    return keys, perm
+
+
+def layer_plans(children, n_rows: int):
+    """`sort_plan` of every DAG layer's child ids (`children`, ids < n_rows, in processing order) from ONE stable sort of the
+    layer-major keys layer * n_rows + child: [(sorted child ids, their positions in the layer's list)]. On the device, no read-back."""
+    sizes = [int(c.numel()) for c in children]
+    if not sum(sizes):
+        return [(c, c) for c in children]
+    keys, perm = sort_plan(torch.cat([c + l * n_rows for l, c in enumerate(children)]))
+    child = keys.remainder_(n_rows) if len(children) > 1 else keys
+    out, off = [], 0
+    for n in sizes:
+        out.append((child[off:off + n], perm[off:off + n] - off))
+        off += n
+    return out
+
+
+def rows_op(op: int, idx: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor | None = None, binding=None, perm: torch.Tensor | None = None) -> None:
     """`sss_rows_op` (include/sss.h; csrc/sss_rows.h): `a` f32[n, width] is the list side (a column slice of a wider row-major
-    matrix is allowed), `b` / `c` f32[rows, width] contiguous tables, `idx` i64[n]"""
+    matrix is allowed), `b` / `c` f32[rows, width] contiguous tables, `idx` i64[n]; `perm` i64[n] (ROWS_ORDERED_ADD only, None: the
+    identity) - idx non-decreasing there"""
     import ctypes
 
     from .binding import SssRowsArgs, device_of
@@ -108,8 +138,12 @@ def rows_op(op: int, idx: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: tor
     assert idx.dtype == torch.int64 and idx.numel() == (n + 1 if op == ROWS_SEGMENT_SUM else n)
     assert a.dtype == b.dtype == torch.float32 and a.stride(1) == 1 and b.is_contiguous() and b.dim() == 2 and b.shape[1] == width
     assert c is None or (c.dtype == torch.float32 and c.is_contiguous() and c.shape == b.shape)
+    if perm is not None:
+        perm = perm.contiguous()
+        assert op == ROWS_ORDERED_ADD and perm.dtype == torch.int64 and perm.numel() == n
     dev = b.device
-    args = SssRowsArgs(n, a.stride(0) if a.shape[0] > 1 else max(width, a.stride(0)), width, op, idx.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr() if c is not None else None)
+    args = SssRowsArgs(n, a.stride(0) if a.shape[0] > 1 else max(width, a.stride(0)), width, op, idx.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr() if c is not None else None,
+                       perm.data_ptr() if perm is not None else None)
     with device_of(dev):
         bnd.check(bnd.lib.sss_rows_op(ctypes.byref(args), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0))
 
@@ -118,8 +152,19 @@ def _rows_ok(t: torch.Tensor, n: int) -> bool:
     return t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and 1 <= t.shape[1] <= 64 and n >= MIN_ROWS
 
 
+def _ordered_add(idx: torch.Tensor, a: torch.Tensor, table: torch.Tensor, is_sorted: bool = False) -> None:
+    """table[idx[i]] += a[i] for every i, the rows of a table row added in list order (`ROWS_ORDERED_ADD`; idx sorted first unless
+    the caller knows it is non-decreasing)"""
+    if is_sorted:
+        rows_op(ROWS_ORDERED_ADD, idx, a, table)
+    else:
+        keys, perm = sort_plan(idx)
+        rows_op(ROWS_ORDERED_ADD, keys, a, table, perm=perm)
+
+
 class _GatherRowsFn(torch.autograd.Function):
-    """table[idx] (rows); backward: the gradient rows are added into a zero table with float atomics"""
+    """table[idx] (rows); backward: the gradient rows are added into a zero table with float atomics (deterministic mode: in a
+    fixed order, `_ordered_add`)"""
 
     @staticmethod
     def forward(ctx, table, idx, unique):
@@ -136,7 +181,10 @@ class _GatherRowsFn(torch.autograd.Function):
         if g.stride(1) != 1 or (g.stride(0) < g.shape[1] and g.shape[0] > 1):  # (an expanded gradient)
             g = g.contiguous()
         gt = torch.zeros((ctx.rows, g.shape[1]), dtype=torch.float32, device=g.device)
-        rows_op(ROWS_SCATTER if ctx.unique else ROWS_SCATTER_ADD, idx, g, gt)
+        if not ctx.unique and deterministic_enabled():
+            _ordered_add(idx, g, gt)
+        else:
+            rows_op(ROWS_SCATTER if ctx.unique else ROWS_SCATTER_ADD, idx, g, gt)
         return gt, None, None
 
 
@@ -148,7 +196,8 @@ def segment_offsets(idx: torch.Tensor, n_seg: int) -> torch.Tensor:
 class _SegmentSumFn(torch.autograd.Function):
     """out[idx[i]] += y[i] into a zero [n_seg, width] table; backward: the gradient of a row is its segment's.
     mode "sorted": idx is non-decreasing - every segment is a range of rows, summed in row order without atomics;
-    mode "unique": idx has no repeats - plain stores; else float atomics"""
+    mode "unique": idx has no repeats - plain stores; else float atomics (deterministic mode: a stable sort, then the rows of a
+    segment added in their list order)"""
 
     @staticmethod
     def forward(ctx, y, idx, n_seg, mode):
@@ -159,7 +208,10 @@ class _SegmentSumFn(torch.autograd.Function):
             rows_op(ROWS_SEGMENT_SUM, segment_offsets(idx, n_seg), y, out)
         else:
             out = torch.zeros((n_seg, y.shape[1]), dtype=torch.float32, device=y.device)
-            rows_op(ROWS_SCATTER if mode == "unique" else ROWS_SCATTER_ADD, idx, y, out)
+            if mode != "unique" and deterministic_enabled():
+                _ordered_add(idx, y, out)
+            else:
+                rows_op(ROWS_SCATTER if mode == "unique" else ROWS_SCATTER_ADD, idx, y, out)
         ctx.save_for_backward(idx)
         return out
 
@@ -220,10 +272,11 @@ class _ConcatRowsFn(torch.autograd.Function):
     """cat([t_0[idx_0], t_1[idx_1], ...], -1) written by one launch over the flat result (no intermediate rows, no copy into the
     concatenation, whole memory transactions); backward: one launch that reads the gradient rows once and adds every part's
     columns into its table. (`CONCAT_ONE_LAUNCH = False`, or more than four parts: one gather / scatter-add per part on column
-    slices - the form of rounds 4-5.)"""
+    slices - the form of rounds 4-5.) Deterministic mode: per part, the column slice itself (no indices) or `_ordered_add` of it
+    (`sorted_mask[k]`: the caller knows idx_k is non-decreasing - no sort)."""
 
     @staticmethod
-    def forward(ctx, n_parts, *args):
+    def forward(ctx, n_parts, sorted_mask, *args):
         tables, idxs = [t.contiguous() for t in args[:n_parts]], list(args[n_parts:])
         n = idxs[0].numel()
         out = torch.empty((n, sum(t.shape[1] for t in tables)), dtype=torch.float32, device=tables[0].device)
@@ -237,36 +290,55 @@ class _ConcatRowsFn(torch.autograd.Function):
                 off += t.shape[1]
         ctx.save_for_backward(*idxs)
         ctx.shapes = [tuple(t.shape) for t in tables]
+        ctx.sorted_mask = sorted_mask
         return out
 
     @staticmethod
     def backward(ctx, g):
         idxs = ctx.saved_tensors
+        if deterministic_enabled():
+            g = g.contiguous()
+            grads, off = [], 0
+            for k, (shape, ix) in enumerate(zip(ctx.shapes, idxs)):
+                gk = None
+                if ctx.needs_input_grad[2 + k]:
+                    if ix is None:  # (row i of the part is row i of the result)
+                        gk = g[:, off:off + shape[1]].contiguous()
+                    else:
+                        gk = torch.zeros(shape, dtype=torch.float32, device=g.device)
+                        _ordered_add(ix, g[:, off:off + shape[1]], gk, ctx.sorted_mask[k])
+                grads.append(gk)
+                off += shape[1]
+            return (None, None, *grads, *([None] * len(idxs)))
         if ctx.one:
             g = g.contiguous()
-            grads = [torch.zeros(shape, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1 + k] else None for k, shape in enumerate(ctx.shapes)]
+            grads = [torch.zeros(shape, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2 + k] else None for k, shape in enumerate(ctx.shapes)]
             if any(t is not None for t in grads):
                 rows_concat(1, g, [t if t is not None else shape[1] for t, shape in zip(grads, ctx.shapes)], list(idxs))
-            return (None, *grads, *([None] * len(idxs)))
+            return (None, None, *grads, *([None] * len(idxs)))
         if g.stride(1) != 1:
             g = g.contiguous()
         grads, off = [], 0
         for k, (shape, ix) in enumerate(zip(ctx.shapes, idxs)):
-            if ctx.needs_input_grad[1 + k]:
+            if ctx.needs_input_grad[2 + k]:
                 gt = torch.zeros(shape, dtype=torch.float32, device=g.device)
                 rows_op(ROWS_SCATTER_ADD, ix, g[:, off:off + shape[1]], gt)
                 grads.append(gt)
             else:
                 grads.append(None)
             off += shape[1]
-        return (None, *grads, *([None] * len(idxs)))
+        return (None, None, *grads, *([None] * len(idxs)))
 
 
-def concat_rows(parts) -> torch.Tensor:
-    """`torch.cat([t.index_select(0, idx) for t, idx in parts], -1)`; on the row kernels when large, float32, on the GPU"""
+def concat_rows(parts, sorted_idx=False) -> torch.Tensor:
+    """`torch.cat([t.index_select(0, idx) for t, idx in parts], -1)`; on the row kernels when large, float32, on the GPU.
+    `sorted_idx`: what the caller knows about the indices - True (all non-decreasing) or one bool per part; the deterministic
+    mode's backward pass sorts the others"""
     n = parts[0][1].numel()
     if all(_rows_ok(t, n) for t, _ in parts) and torch.is_grad_enabled():
-        return _ConcatRowsFn.apply(len(parts), *[t for t, _ in parts], *[ix.contiguous() for _, ix in parts])
+        mask = tuple(bool(v) for v in sorted_idx) if isinstance(sorted_idx, (tuple, list)) else (bool(sorted_idx),) * len(parts)
+        assert len(mask) == len(parts)
+        return _ConcatRowsFn.apply(len(parts), mask, *[t for t, _ in parts], *[ix.contiguous() for _, ix in parts])
     return torch.cat([t.index_select(0, ix) for t, ix in parts], -1)
 
 
@@ -580,7 +652,8 @@ class _MessagePassFn(torch.autograd.Function):
     buffer (rows of receivers are taken out and cleared, gather gradients are added in), both MLPs run on the MLP kernels
     into slices of per-call buffers - so that their six weight gradients are six `sss_linear_wgrad` calls over all layers
     together. `layers`: [(child ids of the layer's edges, position of each edge's receiver in `recv`, recv)], in
-    processing order."""
+    processing order. Deterministic mode: the message gradients are added into their children in a fixed order
+    (`ROWS_ORDERED_ADD` on the layers' `layer_plans`, made by one sort in the forward pass) instead of with float atomics."""
 
     DIMS = (16, 32, 16, 16)
 
@@ -618,6 +691,7 @@ class _MessagePassFn(torch.autograd.Function):
             rows_op(ROWS_UPDATE, recv, uy, h, h_init)  # h[recv] = uy + h_init[recv] (every read of the layer came before this write)
             eo, ro = eo + n_e, ro + n_r
         ctx.layers, ctx.slope, ctx.keep = layers, slope, keep
+        ctx.plans = layer_plans([c for c, _, _ in layers], int(h.shape[0])) if deterministic_enabled() else None
         if keep:
             ctx.save_for_backward(mx, ma1, ma2, ux, ua1, ua2, packed_msg, packed_upd)
         else:
@@ -643,7 +717,11 @@ class _MessagePassFn(torch.autograd.Function):
         gh = gh_in.contiguous().clone()  # gradient w.r.t. the embeddings as they were before the layer being undone
         g_init = torch.zeros_like(gh)
         eo, ro = int(mx.shape[0]), int(ux.shape[0])
-        for child, pos, recv in reversed(layers):
+        plans = ctx.plans
+        if plans is None and deterministic_enabled():  # (the flag was switched on between the two passes)
+            plans = layer_plans([c for c, _, _ in layers], int(gh.shape[0]))
+        for li in range(len(layers) - 1, -1, -1):
+            child, pos, recv = layers[li]
             n_e, n_r = int(child.numel()), int(recv.numel())
             if n_e == 0 or n_r == 0:
                 continue
@@ -661,7 +739,10 @@ class _MessagePassFn(torch.autograd.Function):
                 g_xs = mlp_backward_wgrad(g_msg, mx[eo:eo + n_e], sl(ma1, eo, n_e), sl(ma2, eo, n_e), packed_msg, D, slope, acc_m)
             else:
                 _, _, g_xs = mlp_backward(g_msg, ma1[eo:eo + n_e], ma2[eo:eo + n_e], packed_msg, D, 0, slope, g1=mg1[eo:eo + n_e], g2=mg2[eo:eo + n_e])
-            rows_op(ROWS_SCATTER_ADD, child, g_xs, gh)
+            if plans is not None:  # every child's message gradients in the layer's edge order
+                rows_op(ROWS_ORDERED_ADD, plans[li][0], g_xs, gh, perm=plans[li][1])
+            else:
+                rows_op(ROWS_SCATTER_ADD, child, g_xs, gh)
         if fused:
             return (g_init, gh, None, None, None, None) + tuple(mlp_wgrad_finish(D, acc_m)) + tuple(mlp_wgrad_finish(D, acc_u))
         grads = []

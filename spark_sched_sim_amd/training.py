@@ -14,6 +14,7 @@ steps are always a prefix). Observation (t, b) is observation id t*B + b of `gra
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass, field
 from typing import Any, Callable, Sequence
 
@@ -762,6 +763,24 @@ class PPO:
         return {"policy loss": abs(float(np.mean(pol))), "entropy": abs(float(np.mean(ent))), "approx kl div": abs(float(np.mean(kls))), "minibatches": len(pol)}
 
 
+@contextlib.contextmanager
+def deterministic_scope(fill_uninitialized_memory: bool = False):
+    """`torch.use_deterministic_algorithms(True)` for the duration of the block, with torch's
+    `torch.utils.deterministic.fill_uninitialized_memory` set as given (False by default: its fills would write every `empty`
+    buffer of a multi-GB update, and no result here depends on that memory). Both are restored on exit, also when an exception
+    escapes. The row kernels of the update read the flag at every call (train_kernels.deterministic_enabled)."""
+    import torch.utils.deterministic as tud
+
+    prev, prev_warn, prev_fill = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled(), tud.fill_uninitialized_memory
+    torch.use_deterministic_algorithms(True)
+    tud.fill_uninitialized_memory = fill_uninitialized_memory
+    try:
+        yield
+    finally:
+        tud.fill_uninitialized_memory = prev_fill
+        torch.use_deterministic_algorithms(prev, warn_only=prev_warn)
+
+
 class Trainer:
     """the reference's training loop (trainers/trainer.py:27-168) with the rollout workers replaced
     by the batched env: per iteration collect `num_sequences x num_rollouts` rollouts (per rank),
@@ -771,11 +790,16 @@ class Trainer:
     sequences of its own (base seeds are a function of the global sequence id, so the union over
     ranks does not depend on the placement), rollouts of one sequence stay on one rank (their
     baseline needs no traffic), gradients are averaged across ranks and ONE all-gather per
-    iteration moves the per-rollout statistics (trainer.py:113-121's Pipe gather)."""
+    iteration moves the per-rollout statistics (trainer.py:113-121's Pipe gather).
+
+    Deterministic mode (`deterministic=True`, or the `deterministic` key of the trainer section): `train()` runs inside
+    `deterministic_scope()`, so that the same config, seed and record give the same parameters bit for bit on the same software
+    and hardware. Not verified across several ranks (the collective's reduction order is the library's)."""
 
     def __init__(self, agent_cfg: dict[str, Any], env_cfg: dict[str, Any], train_cfg: dict[str, Any],
-                 device: str | torch.device | None = None, _lib=None, pack: bytes | None = None):
-        """`pack`: the workload pack the envs run on (None: the frozen default trace set)"""
+                 device: str | torch.device | None = None, _lib=None, pack: bytes | None = None, deterministic: bool | None = None):
+        """`pack`: the workload pack the envs run on (None: the frozen default trace set); `deterministic`: None reads
+        train_cfg["deterministic"] (default False)"""
         import torch.distributed as dist
 
         from .decima import DecimaPolicy
@@ -789,6 +813,11 @@ class Trainer:
         self.num_sequences = int(train_cfg["num_sequences"])
         self.num_rollouts = int(train_cfg["num_rollouts"])
         self.rollout_duration = train_cfg.get("rollout_duration")
+        self.deterministic = bool(train_cfg.get("deterministic", False) if deterministic is None else deterministic)
+        if self.deterministic and self.rollout_duration:
+            raise ValueError("trainer: `deterministic: true` cannot be combined with `rollout_duration` (asynchronous collection is paced by the wall clock)")
+        if self.deterministic and int(train_cfg.get("collector_groups", 1)) > 1:
+            raise ValueError("trainer: `deterministic: true` needs `collector_groups: 1` (several groups of envs on their own streams are not verified to be reproducible)")
         self.checkpointing_freq = int(train_cfg.get("checkpointing_freq", 50))
         self.artifacts_dir = train_cfg.get("artifacts_dir", "artifacts")
         self.env_cfg = dict(env_cfg)
@@ -839,6 +868,12 @@ class Trainer:
         return {k: arr[:, i] for i, k in enumerate(keys)}
 
     def train(self, verbose: bool = True) -> list[dict[str, float]]:
+        if self.deterministic:
+            with deterministic_scope():
+                return self._train(verbose)
+        return self._train(verbose)
+
+    def _train(self, verbose: bool) -> list[dict[str, float]]:
         import json
         import os
         import os.path as osp

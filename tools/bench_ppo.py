@@ -11,7 +11,7 @@ import time
 import torch
 
 sys.path.insert(0, osp.dirname(osp.dirname(osp.abspath(__file__))))
-from spark_sched_sim_amd.training import Trainer  # noqa: E402
+from spark_sched_sim_amd.training import Trainer, deterministic_scope  # noqa: E402
 
 AGENT = dict(agent_cls="DecimaScheduler", embed_dim=16,
              gnn_mlp_kwargs=dict(hid_dims=[32, 16], act_cls="LeakyReLU", act_kwargs=dict(negative_slope=0.2)),
@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--device-index", type=int, default=None)
     ap.add_argument("--collector-groups", type=int, default=1)
+    ap.add_argument("--deterministic", action="store_true", help="the trainer's deterministic mode (`trainer: deterministic: true`): the iterations run "
+                    "under training.deterministic_scope, the update's row sums in a fixed order")
     ap.add_argument("--no-train", action="store_true", help="collections only (for a rocprofv3 kernel trace of the collection alone: tools/profile_ppo_rocprof.sh)")
     ap.add_argument("--kernel-switch", action="append", default=[], metavar="NAME=0|1",
                     help="set a module-level switch of spark_sched_sim_amd.train_kernels (FUSED_HEAD_WGRAD, CONCAT_ONE_LAUNCH, SPLIT_INPUT, INDEXED_ROWS, ...): A/B timing")
@@ -47,7 +49,7 @@ def main():
     train = dict(trainer_cls="PPO", num_iterations=1, num_sequences=a.sequences, num_rollouts=a.rollouts, seed=42,
                  checkpointing_freq=10 ** 9, num_epochs=3, num_batches=10, clip_range=0.2, target_kl=0.01, entropy_coeff=0.04,
                  beta_discount=5.0e-3, opt_cls="Adam", opt_kwargs=dict(lr=3.0e-4), max_grad_norm=0.5, artifacts_dir="/tmp/sss_ppo",
-                 collector_groups=a.collector_groups)
+                 collector_groups=a.collector_groups, deterministic=a.deterministic)
     if a.rollout_duration:
         train["rollout_duration"] = a.rollout_duration
     env = dict(num_executors=a.executors, job_arrival_cap=a.jobs, job_arrival_rate=4.0e-5, moving_delay=2000.0,
@@ -61,21 +63,23 @@ def main():
         dist.init_process_group(a.dist_backend)
     tr = Trainer(AGENT, env, train, device=dev)
     out = []
-    for it in range(a.iterations):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        tr.policy.eval()
-        ro = tr.collector.collect_async(a.rollout_duration, with_stats=False) if a.rollout_duration else tr.collector.collect_sync(with_stats=False)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        tr.policy.train()
-        learn = {} if a.no_train else tr.ppo.train_on_rollouts(ro)
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        n = int(ro.active.sum())
-        out.append({"iteration": it, "n_gpus": world, "envs_per_gpu": a.sequences * a.rollouts, "envs": a.sequences * a.rollouts, "samples": n, "longest_rollout": int(ro.active.shape[0]),
-                    "collect_s": t1 - t0, "train_s": t2 - t1, "collect_env_steps_per_s": n / (t1 - t0),
-                    "graph_nodes": int(ro.graph["x"].shape[0]), **learn})
+    import contextlib
+    with deterministic_scope() if a.deterministic else contextlib.nullcontext():
+        for it in range(a.iterations):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tr.policy.eval()
+            ro = tr.collector.collect_async(a.rollout_duration, with_stats=False) if a.rollout_duration else tr.collector.collect_sync(with_stats=False)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            tr.policy.train()
+            learn = {} if a.no_train else tr.ppo.train_on_rollouts(ro)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            n = int(ro.active.sum())
+            out.append({"iteration": it, "n_gpus": world, "envs_per_gpu": a.sequences * a.rollouts, "envs": a.sequences * a.rollouts, "samples": n, "longest_rollout": int(ro.active.shape[0]),
+                        "collect_s": t1 - t0, "train_s": t2 - t1, "collect_env_steps_per_s": n / (t1 - t0),
+                        "graph_nodes": int(ro.graph["x"].shape[0]), "deterministic": a.deterministic, **learn})
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
