@@ -617,6 +617,53 @@ typedef struct sss_baseline_args {
 int sss_discounted_returns(const sss_returns_args* a, void* stream);
 int sss_sequence_baselines(const sss_baseline_args* a, void* stream);
 
+/* Differential (average-reward) returns over the same [T][B] record, in two calls so that several ranks can pool their sums
+ * between them (one all-reduce of sums_dev). Everything is f64 on the CURRENT device; nothing comes back to the host.
+ *   sss_reward_window_update  the moving window of (dt, reward) rows behind `avg_num_jobs` - the CircularArray of
+ *                             trainers/utils/returns_calculator.py:6-22, fed as in :52-55 - as f64[cap][2], zero before the first
+ *                             call. The record's rows (t_after - t_before, reward) with dt > 0 are taken env by env (env 0's active
+ *                             steps in step order, then env 1's, ...: the reference's chain(*deltas_list)); of more than cap new
+ *                             rows the last cap count; the window's last cap - n rows move to its front and the n new rows follow.
+ *                             window_dev[current] is the window before the call and is left as it was; the window after the call
+ *                             is window_dev[1 - current] (every row of it is written) - unless T == 0 or B == 0: then nothing
+ *                             moves and the window stays window_dev[current]. The caller keeps count of which one is current.
+ *                             sums_dev[0] = total time, sums_dev[1] = reward sum of the window after the call: each
+ *                             0.0 + row[0] + row[1] + ... + row[cap - 1] in row order over all cap rows (numpy's axis-0 sum of the
+ *                             (cap, 2) array adds in this order; the order is fixed, so the bits are).
+ *                             scratch_dev: SSS_REWARD_WINDOW_SCRATCH(T, B) int64 of workspace, contents irrelevant.
+ *   sss_differential_returns  avg = -sums_dev[1] / sums_dev[0] (nan for a window without rows, as in the reference), written to
+ *                             avg_dev[0] (may be NULL); per env from its last row R = -(-r - dt * avg) + R
+ *                             (returns_calculator.py:52-65, 78-89); out = 0 on rows that are not active. */
+#define SSS_REWARD_WINDOW_CHUNK 64
+#define SSS_REWARD_WINDOW_SCRATCH(T, B) ((((T) + SSS_REWARD_WINDOW_CHUNK - 1) / SSS_REWARD_WINDOW_CHUNK + 1) * (B) + 1)
+struct sss_reward_window_args {
+  int64_t T, B;
+  const uint8_t* active_dev;
+  const double* t_before_dev;
+  const double* t_after_dev;
+  const double* rewards_dev;
+  int64_t cap;            /* rows of the window, >= 1 */
+  double* window_dev[2];  /* f64[cap][2] each, 16-byte aligned (a row is read as one 16-byte load) */
+  int32_t current;        /* 0 or 1 */
+  int32_t pad_;
+  int64_t* scratch_dev;
+  double* sums_dev;       /* f64[2] */
+};
+typedef struct sss_reward_window_args sss_reward_window_args;
+struct sss_diffret_args {
+  int64_t T, B;
+  const uint8_t* active_dev;
+  const double* t_before_dev;
+  const double* t_after_dev;
+  const double* rewards_dev;
+  const double* sums_dev; /* f64[2]: this rank's, or the ranks' sums added up */
+  double* out_dev;        /* f64[T][B] */
+  double* avg_dev;        /* f64[1] or NULL */
+};
+typedef struct sss_diffret_args sss_diffret_args;
+int sss_reward_window_update(const sss_reward_window_args* a, void* stream);
+int sss_differential_returns(const sss_diffret_args* a, void* stream);
+
 /* Row gathers / scatters of the PPO update (what PyG's message passing, the score networks' `torch.cat([x[idx], h[idx], ..])`
  * inputs and the per-job / per-observation sums run as index_select / index_add_ under autograd in the reference:
  * schedulers/decima/scheduler.py:209-232, :246-283, :289-318, :337-385). `a` is the list side (row i, leading dimension ld_a

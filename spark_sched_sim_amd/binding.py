@@ -153,6 +153,24 @@ class SssBaselineArgs(C.Structure):  # include/sss.h sss_baseline_args
                 ("values_dev", C.c_void_p), ("n_dev", C.c_void_p), ("out_dev", C.c_void_p)]
 
 
+class SssRewardWindowArgs(C.Structure):  # include/sss.h sss_reward_window_args
+    _fields_ = [("T", C.c_int64), ("B", C.c_int64), ("active_dev", C.c_void_p), ("t_before_dev", C.c_void_p), ("t_after_dev", C.c_void_p), ("rewards_dev", C.c_void_p),
+                ("cap", C.c_int64), ("window_dev", C.c_void_p * 2), ("current", C.c_int32), ("pad_", C.c_int32), ("scratch_dev", C.c_void_p), ("sums_dev", C.c_void_p)]
+
+
+class SssDiffretArgs(C.Structure):  # include/sss.h sss_diffret_args
+    _fields_ = [("T", C.c_int64), ("B", C.c_int64), ("active_dev", C.c_void_p), ("t_before_dev", C.c_void_p), ("t_after_dev", C.c_void_p), ("rewards_dev", C.c_void_p),
+                ("sums_dev", C.c_void_p), ("out_dev", C.c_void_p), ("avg_dev", C.c_void_p)]
+
+
+REWARD_WINDOW_CHUNK = 64  # include/sss.h SSS_REWARD_WINDOW_CHUNK
+
+
+def reward_window_scratch(T: int, B: int) -> int:
+    """include/sss.h SSS_REWARD_WINDOW_SCRATCH(T, B): int64 elements of workspace of sss_reward_window_update"""
+    return ((T + REWARD_WINDOW_CHUNK - 1) // REWARD_WINDOW_CHUNK + 1) * B + 1
+
+
 class SssArenaArray(C.Structure):  # include/sss.h sss_arena_array
     _fields_ = [("src_dev", C.c_void_p), ("dst_dev", C.c_void_p), ("elem_bytes", C.c_int32), ("per_row", C.c_int32), ("kind", C.c_int32), ("shift", C.c_int32)]
 
@@ -164,7 +182,7 @@ class SssArenaArgs(C.Structure):  # include/sss.h sss_arena_args
 
 EXPORTS = ["sss_query_dims", "sss_create", "sss_bind_buffers", "sss_reset", "sss_step", "sss_step_bounded", "sss_policy", "sss_rollout",
            "sss_decima_graph_build", "sss_decima_layer_lists", "sss_prefix_rows", "sss_decima_policy", "sss_decima_sample", "sss_gnn_launch",
-           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
+           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
 POLICY_IDS = {"fair": 0, "fifo": 1, "hash": 2, "wfair": 3, "sjfcp": 4}
 WFAIR_ALPHA_RANGE = (-4, 4)  # sss_policy / sss_rollout: the weighted-fair exponent (param of policy 3)
 # the argument structures of include/sss.h and their mirrors here (Binding.check_abi)
@@ -173,6 +191,9 @@ ABI_STRUCTS = {"sss_cfg": SssCfg, "sss_dims": SssDims, "sss_buffers": SssBuffers
                "sss_decima_sample_args": SssDecimaSampleArgs, "sss_gnn_encode_args": SssGnnEncodeArgs, "sss_collect_args": SssCollectArgs,
                "sss_mlp_args": SssMlpArgs, "sss_arena_array": SssArenaArray, "sss_arena_args": SssArenaArgs, "sss_returns_args": SssReturnsArgs,
                "sss_baseline_args": SssBaselineArgs, "sss_rows_args": SssRowsArgs, "sss_concat_part": SssConcatPart, "sss_concat_args": SssConcatArgs, "sss_segcat_args": SssSegcatArgs}
+# ... and the ones the header declares as `struct name { .. }; typedef struct name name;` (tests/test_abi.py pins the list of the
+# `} name;` typedefs above against a list of its own): checked at load in the same way
+ABI_TAGGED_STRUCTS = {"sss_reward_window_args": SssRewardWindowArgs, "sss_diffret_args": SssDiffretArgs}
 
 
 def load_library(path: str | None = None) -> C.CDLL:
@@ -219,6 +240,8 @@ class Binding:
         L.sss_mlp_wgrad_finish.argtypes = [C.c_int] + [C.c_void_p] * 8
         L.sss_discounted_returns.argtypes = [C.POINTER(SssReturnsArgs), C.c_void_p]
         L.sss_sequence_baselines.argtypes = [C.POINTER(SssBaselineArgs), C.c_void_p]
+        L.sss_reward_window_update.argtypes = [C.POINTER(SssRewardWindowArgs), C.c_void_p]
+        L.sss_differential_returns.argtypes = [C.POINTER(SssDiffretArgs), C.c_void_p]
         L.sss_bit_lists.argtypes = [C.POINTER(SssBitListArgs), C.c_void_p]
         L.sss_arena_append.argtypes = [C.POINTER(SssArenaArgs), C.c_void_p]
         L.sss_rows_op.argtypes = [C.POINTER(SssRowsArgs), C.c_void_p]
@@ -232,7 +255,7 @@ class Binding:
     def check_abi(self) -> None:
         """every ctypes mirror above has the size the library was compiled with (include/sss.h sss_abi_sizeof): a binding and a
         library of different rounds fail here, not inside a kernel"""
-        bad = [(name, C.sizeof(cls), self.lib.sss_abi_sizeof(name.encode())) for name, cls in ABI_STRUCTS.items()
+        bad = [(name, C.sizeof(cls), self.lib.sss_abi_sizeof(name.encode())) for name, cls in {**ABI_STRUCTS, **ABI_TAGGED_STRUCTS}.items()
                if C.sizeof(cls) != self.lib.sss_abi_sizeof(name.encode())]
         if bad:
             raise RuntimeError("binding / library mismatch (struct, sizeof in binding.py, sizeof in the library): " + ", ".join(map(str, bad)))

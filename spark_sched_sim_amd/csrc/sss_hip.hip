@@ -203,6 +203,26 @@ static int be_launch_baselines(const SssBaselineArgs& a, void* stream) {
   hipLaunchKernelGGL(sss_baseline_kernel, dim3((unsigned)((a.T * a.B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
+// the reward window of the differential returns (sss_returns.h): counts, prefixes, move + scatter - then, as a launch of its own
+// (the window may also be summed without an update), the ordered column sums
+static int be_launch_reward_window(const SssWindowArgs& a, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned cells = (unsigned)((a.n_chunks * a.B + 255) / 256), rows = (unsigned)((a.cap + 255) / 256);
+  hipLaunchKernelGGL(sss_window_count_kernel, dim3(cells), dim3(256), 0, st, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(sss_window_scan_kernel, dim3(1), dim3(WINDOW_SCAN_THREADS), 0, st, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(sss_window_scatter_kernel, dim3(cells > rows ? cells : rows), dim3(256), 0, st, a);
+  return (int)hipGetLastError();
+}
+static int be_launch_window_sums(const double* win, int64_t cap, double* sums, void* stream) {
+  hipLaunchKernelGGL(sss_window_sum_kernel, dim3(1), dim3(WINDOW_SUM_THREADS), 0, (hipStream_t)stream, win, cap, sums);
+  return (int)hipGetLastError();
+}
+static int be_launch_diffret(const SssDiffretArgs& a, void* stream) {
+  hipLaunchKernelGGL(sss_diffret_kernel, dim3((unsigned)(a.B > 0 ? (a.B + 63) / 64 : 1)), dim3(64), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
 #include "sss_arena.h"
 static int be_launch_arena(const SssArenaArgs& a, int64_t rows_hint, void* stream) {
   int64_t bx = rows_hint > 0 ? (rows_hint + 1023) / 1024 : 256;

@@ -323,6 +323,7 @@ extern "C" int sss_abi_sizeof(const char* name) {
   SSS_ABI_SIZE(sss_bit_list_args) SSS_ABI_SIZE(sss_gnn_args) SSS_ABI_SIZE(sss_decima_policy_args) SSS_ABI_SIZE(sss_decima_sample_args)
   SSS_ABI_SIZE(sss_gnn_encode_args) SSS_ABI_SIZE(sss_collect_args) SSS_ABI_SIZE(sss_mlp_args) SSS_ABI_SIZE(sss_arena_array)
   SSS_ABI_SIZE(sss_arena_args) SSS_ABI_SIZE(sss_returns_args) SSS_ABI_SIZE(sss_baseline_args) SSS_ABI_SIZE(sss_rows_args) SSS_ABI_SIZE(sss_concat_part) SSS_ABI_SIZE(sss_concat_args) SSS_ABI_SIZE(sss_segcat_args)
+  SSS_ABI_SIZE(sss_reward_window_args) SSS_ABI_SIZE(sss_diffret_args)
 #undef SSS_ABI_SIZE
   return -1;
 }
@@ -842,6 +843,43 @@ extern "C" int sss_sequence_baselines(const sss_baseline_args* a, void* stream) 
   r.T = a->T, r.B = a->B, r.R = a->R, r.skip_empty = a->skip_empty, r.active = a->active_dev, r.times = a->times_dev, r.values = a->values_dev, r.n = a->n_dev, r.out = a->out_dev;
   if (r.T == 0 || r.B == 0) return 0;
   if (int rc = be_launch_baselines(r, stream)) return sss_fail(-30, std::string("baselines launch failed: ") + be_error(rc));
+  return 0;
+}
+
+// the differential returns' two halves (sss_returns.h). Their launches (be_launch_reward_window / _window_sums / _diffret) are
+// the HIP unit's, or - without a device compiler - that header's plain loops.
+static_assert(SSS_REWARD_WINDOW_CHUNK == WINDOW_CHUNK, "include/sss.h sizes the scratch by the kernels' chunk");
+extern "C" int sss_reward_window_update(const sss_reward_window_args* a, void* stream) {
+  if (!a || !a->window_dev[0] || !a->window_dev[1] || !a->sums_dev) return sss_fail(-1, "NULL argument");
+  if (a->T < 0 || a->B < 0) return sss_fail(-39, "sss_reward_window_update: negative size");
+  if (a->cap < 1) return sss_fail(-39, "sss_reward_window_update: cap must be >= 1");
+  if (a->current != 0 && a->current != 1) return sss_fail(-39, "sss_reward_window_update: current must be 0 or 1");
+  if (a->window_dev[0] == a->window_dev[1]) return sss_fail(-39, "sss_reward_window_update: the two window buffers must differ");
+  if (((uintptr_t)a->window_dev[0] | (uintptr_t)a->window_dev[1]) & 15) return sss_fail(-39, "sss_reward_window_update: the window buffers must be 16-byte aligned");
+  const double* win = a->window_dev[a->current];
+  if (a->T > 0 && a->B > 0) {
+    if (!a->active_dev || !a->t_before_dev || !a->t_after_dev || !a->rewards_dev || !a->scratch_dev) return sss_fail(-1, "NULL argument");
+    SssWindowArgs r;
+    r.T = a->T, r.B = a->B, r.cap = a->cap, r.active = a->active_dev, r.t_before = a->t_before_dev, r.t_after = a->t_after_dev, r.rewards = a->rewards_dev;
+    r.src = win, r.dst = a->window_dev[1 - a->current];
+    r.n_chunks = (a->T + WINDOW_CHUNK - 1) / WINDOW_CHUNK;
+    r.pre = a->scratch_dev, r.env_off = r.pre + r.n_chunks * r.B, r.n_new = r.env_off + r.B;
+    if (int rc = be_launch_reward_window(r, stream)) return sss_fail(-30, std::string("reward window launch failed: ") + be_error(rc));
+    win = r.dst;
+  }
+  if (int rc = be_launch_window_sums(win, a->cap, a->sums_dev, stream)) return sss_fail(-30, std::string("window sums launch failed: ") + be_error(rc));
+  return 0;
+}
+extern "C" int sss_differential_returns(const sss_diffret_args* a, void* stream) {
+  if (!a || !a->sums_dev) return sss_fail(-1, "NULL argument");
+  if (a->T < 0 || a->B < 0) return sss_fail(-39, "sss_differential_returns: negative size");
+  const bool empty = a->T == 0 || a->B == 0;
+  if (!empty && (!a->active_dev || !a->t_before_dev || !a->t_after_dev || !a->rewards_dev || !a->out_dev)) return sss_fail(-1, "NULL argument");
+  SssDiffretArgs r;
+  r.T = a->T, r.B = empty ? 0 : a->B, r.active = a->active_dev, r.t_before = a->t_before_dev, r.t_after = a->t_after_dev, r.rewards = a->rewards_dev;
+  r.sums = a->sums_dev, r.out = a->out_dev, r.avg = a->avg_dev;
+  if (empty && !a->avg_dev) return 0;
+  if (int rc = be_launch_diffret(r, stream)) return sss_fail(-30, std::string("differential returns launch failed: ") + be_error(rc));
   return 0;
 }
 

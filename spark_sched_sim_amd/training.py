@@ -480,6 +480,11 @@ def _record_kernels(ro: Rollouts, binding=None):
     return None
 
 
+def _dist_world() -> int:
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
 def _c64(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous() if t.dtype == torch.float64 else t.double().contiguous()
 
@@ -508,9 +513,20 @@ def discounted_returns(ro: Rollouts, beta: float, binding=None) -> torch.Tensor:
     return out * ro.active
 
 
+def _pool_window_sums(sums: torch.Tensor) -> torch.Tensor:
+    """several ranks: the ranks' (total time, reward sum) added up, in place - every rank then uses the same
+    avg_num_jobs = -sum(rew) / sum(time) over all ranks' windows (the reference's one learner keeps ONE window over every worker's
+    rows; here each rank keeps `cap` rows of its own envs and the estimate is pooled: DESIGN section 7). One process: untouched."""
+    import torch.distributed as dist
+    if _dist_world() > 1:
+        dist.all_reduce(sums)
+    return sums
+
+
 class DifferentialReturns:
     """average-reward ("differential") returns with the moving estimate of the mean number of
-    concurrent jobs kept in a circular buffer of (dt, reward) rows (returns_calculator.py:6-65, 78-89)"""
+    concurrent jobs kept in a circular buffer of (dt, reward) rows (returns_calculator.py:6-65, 78-89).
+    The host form: the rows go to the host and the window is a numpy array (`DeviceDifferentialReturns`: the kernels)"""
 
     def __init__(self, buff_cap: int):
         self.cap = int(buff_cap)
@@ -530,6 +546,9 @@ class DifferentialReturns:
         rows = np.stack([ro.flat(dt).cpu().numpy(), ro.flat(ro.rewards).cpu().numpy()], 1)
         self._extend(rows[rows[:, 0] > 0])
         total_time, rew_sum = self.data.sum(0)
+        if _dist_world() > 1:
+            total_time, rew_sum = _pool_window_sums(torch.tensor([total_time, rew_sum], dtype=torch.float64, device=ro.rewards.device)).tolist()
+            total_time, rew_sum = np.float64(total_time), np.float64(rew_sum)  # (numpy's division: 0 / 0 is nan, not an exception)
         self.avg_num_jobs = -rew_sum / total_time
         T, B = ro.active.shape
         out = torch.zeros_like(ro.rewards)
@@ -539,6 +558,60 @@ class DifferentialReturns:
             R = torch.where(ro.active[k], -(-ro.rewards[k] - dt[k] * self.avg_num_jobs) + R, R)
             out[k] = R
         return out * ro.active
+
+
+class DeviceDifferentialReturns:
+    """`DifferentialReturns` on the record's device (include/sss.h sss_reward_window_update / sss_differential_returns; csrc/
+    sss_returns.h): the window is a pair of f64[cap][2] device buffers used in turn, its sums are taken in row order (the bits of
+    the host class's numpy sum), and the call makes no device->host transfer and no synchronisation. `avg_num_jobs` reads the
+    device scalar when asked. `binding`: as for `discounted_returns` (tests: the emulator's host backend)."""
+
+    def __init__(self, buff_cap: int, binding=None):
+        self.cap = int(buff_cap)
+        if self.cap < 1:
+            raise ValueError("reward_buff_cap must be >= 1")
+        self.binding = binding
+        self._win: torch.Tensor | None = None   # f64[2, cap, 2]: the window is _win[_cur]
+        self._cur = 0
+        self._sums: torch.Tensor | None = None  # f64[2] total time, reward sum (pooled over the ranks)
+        self._avg: torch.Tensor | None = None   # f64[1]
+
+    @property
+    def avg_num_jobs(self) -> float | None:
+        return None if self._avg is None else float(self._avg)
+
+    @property
+    def data(self) -> np.ndarray:
+        """the window's rows (a host copy)"""
+        return np.zeros((self.cap, 2)) if self._win is None else self._win[self._cur].cpu().numpy()
+
+    def __call__(self, ro: Rollouts) -> torch.Tensor:
+        import ctypes
+
+        from .binding import SssDiffretArgs, SssRewardWindowArgs, device_of, reward_window_scratch
+        b = _record_kernels(ro, self.binding)
+        if b is None:
+            raise RuntimeError("DeviceDifferentialReturns: the record is not on a GPU and no binding was given (DifferentialReturns is the host form)")
+        T, B = ro.active.shape
+        dev = ro.active.device
+        if self._win is None:
+            self._win = torch.zeros((2, self.cap, 2), dtype=torch.float64, device=dev)
+            self._sums = torch.empty(2, dtype=torch.float64, device=dev)
+            self._avg = torch.empty(1, dtype=torch.float64, device=dev)
+        act, tb, ta, rw = ro.active.contiguous().view(torch.uint8), _c64(ro.t_before), _c64(ro.t_after), _c64(ro.rewards)
+        scratch = torch.empty(reward_window_scratch(T, B), dtype=torch.int64, device=dev)
+        out = torch.empty((T, B), dtype=torch.float64, device=dev)
+        w = SssRewardWindowArgs(T, B, act.data_ptr(), tb.data_ptr(), ta.data_ptr(), rw.data_ptr(), self.cap,
+                                (ctypes.c_void_p * 2)(self._win[0].data_ptr(), self._win[1].data_ptr()), self._cur, 0, scratch.data_ptr(), self._sums.data_ptr())
+        d = SssDiffretArgs(T, B, act.data_ptr(), tb.data_ptr(), ta.data_ptr(), rw.data_ptr(), self._sums.data_ptr(), out.data_ptr(), self._avg.data_ptr())
+        with device_of(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+            b.check(b.lib.sss_reward_window_update(ctypes.byref(w), stream))
+            if T > 0 and B > 0:
+                self._cur = 1 - self._cur  # (the update wrote the other buffer)
+            _pool_window_sums(self._sums)
+            b.check(b.lib.sss_differential_returns(ctypes.byref(d), stream))
+        return out
 
 
 # ---- baselines (trainers/utils/baselines.py) --------------------------------------------------------
@@ -604,7 +677,9 @@ def sequence_baselines(ro: Rollouts, values: torch.Tensor, num_sequences: int, n
         act, ts, ys = ro.active.contiguous().view(torch.uint8), _c64(ro.t_before), _c64(values)
         n = ro.active.sum(0).to(torch.int64).contiguous()
         out = torch.empty((T, B), dtype=torch.float64, device=dev)
-        a = SssBaselineArgs(T, B, R, int(not bool((n > 0).all())), act.data_ptr(), ts.data_ptr(), ys.data_ptr(), n.data_ptr(), out.data_ptr())
+        # (skip_empty always: with every rollout non-empty it multiplies by 1.0 and divides by R, the same bits - and asking the
+        # device whether some rollout is empty would make the host wait for it)
+        a = SssBaselineArgs(T, B, R, 1, act.data_ptr(), ts.data_ptr(), ys.data_ptr(), n.data_ptr(), out.data_ptr())
         with device_of(dev):
             b.check(b.lib.sss_sequence_baselines(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0))
         return out
@@ -667,11 +742,20 @@ class PPO:
         assert ("reward_buff_cap" in train_cfg) ^ ("beta_discount" in train_cfg), \
             "must provide exactly one of `reward_buff_cap` and `beta_discount` in config"  # trainer.py:63-65
         self.beta = train_cfg.get("beta_discount")
+        # differential returns: `diff` starts as the host form; the first record decides (`returns`): on a GPU the kernels take over
         self.diff = DifferentialReturns(train_cfg["reward_buff_cap"]) if "reward_buff_cap" in train_cfg else None
+        self.device_returns = True  # (False: the host form also for a record on a GPU - A/B timing, tools/bench_ppo.py --host-returns)
         self.generator = generator
 
+    def returns(self, ro: Rollouts) -> torch.Tensor:
+        if self.diff is None:
+            return discounted_returns(ro, self.beta)
+        if type(self.diff) is DifferentialReturns and self.diff.avg_num_jobs is None and ro.active.is_cuda and self.device_returns:
+            self.diff = DeviceDifferentialReturns(self.diff.cap)  # (the first record is on a GPU: the kernels, no fallback from here on)
+        return self.diff(ro)
+
     def preprocess(self, ro: Rollouts):
-        returns = self.diff(ro) if self.diff is not None else discounted_returns(ro, self.beta)
+        returns = self.returns(ro)
         baselines = sequence_baselines(ro, returns, self.num_sequences, self.num_rollouts)
         return returns, baselines
 

@@ -33,6 +33,13 @@ def main():
     ap.add_argument("--collector-groups", type=int, default=1)
     ap.add_argument("--deterministic", action="store_true", help="the trainer's deterministic mode (`trainer: deterministic: true`): the iterations run "
                     "under training.deterministic_scope, the update's row sums in a fixed order")
+    ap.add_argument("--differential", type=int, nargs="?", const=200_000, default=None, metavar="CAP",
+                    help="differential (average-reward) returns: `reward_buff_cap: CAP` (default 200000, the value the reference's config keeps commented) "
+                    "in place of `beta_discount`")
+    ap.add_argument("--host-returns", action="store_true", help="with --differential: training.DifferentialReturns, the host form (rows copied to the host, a "
+                    "Python loop over the steps), in place of the kernels: A/B timing")
+    ap.add_argument("--time-returns", action="store_true", help="report the returns step's time (`returns_s`) with discounted returns too: two more device "
+                    "synchronises inside train_s (--differential always reports it)")
     ap.add_argument("--no-train", action="store_true", help="collections only (for a rocprofv3 kernel trace of the collection alone: tools/profile_ppo_rocprof.sh)")
     ap.add_argument("--kernel-switch", action="append", default=[], metavar="NAME=0|1",
                     help="set a module-level switch of spark_sched_sim_amd.train_kernels (FUSED_HEAD_WGRAD, CONCAT_ONE_LAUNCH, SPLIT_INPUT, INDEXED_ROWS, ...): A/B timing")
@@ -52,6 +59,9 @@ def main():
                  collector_groups=a.collector_groups, deterministic=a.deterministic)
     if a.rollout_duration:
         train["rollout_duration"] = a.rollout_duration
+    if a.differential is not None:
+        del train["beta_discount"]
+        train["reward_buff_cap"] = a.differential
     env = dict(num_executors=a.executors, job_arrival_cap=a.jobs, job_arrival_rate=4.0e-5, moving_delay=2000.0,
                warmup_delay=1000.0, mean_time_limit=a.mean_time_limit)  # config/decima_tpch.yaml:80-86
     import os
@@ -62,6 +72,23 @@ def main():
         import torch.distributed as dist
         dist.init_process_group(a.dist_backend)
     tr = Trainer(AGENT, env, train, device=dev)
+    if a.host_returns:
+        assert a.differential is not None, "--host-returns goes with --differential"
+        tr.ppo.device_returns = False
+    # the returns step of the update (PPO.preprocess' first half) timed on its own, between two device synchronises of its own (they
+    # sit inside train_s: only where the step's time is asked for)
+    returns_s = []
+    if a.differential is not None or a.time_returns:
+        step = tr.ppo.returns
+
+        def timed_returns(ro):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = step(ro)
+            torch.cuda.synchronize()
+            returns_s.append(time.perf_counter() - t)
+            return res
+        tr.ppo.returns = timed_returns
     out = []
     import contextlib
     with deterministic_scope() if a.deterministic else contextlib.nullcontext():
@@ -79,7 +106,9 @@ def main():
             n = int(ro.active.sum())
             out.append({"iteration": it, "n_gpus": world, "envs_per_gpu": a.sequences * a.rollouts, "envs": a.sequences * a.rollouts, "samples": n, "longest_rollout": int(ro.active.shape[0]),
                         "collect_s": t1 - t0, "train_s": t2 - t1, "collect_env_steps_per_s": n / (t1 - t0),
-                        "graph_nodes": int(ro.graph["x"].shape[0]), "deterministic": a.deterministic, **learn})
+                        "graph_nodes": int(ro.graph["x"].shape[0]), "deterministic": a.deterministic,
+                        "returns": "discounted" if a.differential is None else ("differential, host" if a.host_returns else "differential, device"),
+                        "reward_buff_cap": a.differential, "returns_s": returns_s[-1] if returns_s and not a.no_train else None, **learn})
     if rank == 0:
         print(json.dumps(out))
     if world > 1:

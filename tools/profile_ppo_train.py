@@ -40,7 +40,7 @@ def main():
     # pieces of one minibatch
     ppo = tr.ppo
     torch.cuda.synchronize(); p0 = time.perf_counter()
-    returns = ppo.diff(ro) if ppo.diff is not None else discounted_returns(ro, ppo.beta)
+    returns = ppo.returns(ro)
     torch.cuda.synchronize(); p1 = time.perf_counter()
     baselines = sequence_baselines(ro, returns, ppo.num_sequences, ppo.num_rollouts)
     torch.cuda.synchronize(); p2 = time.perf_counter()
