@@ -743,6 +743,44 @@ typedef struct sss_segcat_args {
 } sss_segcat_args;
 int sss_segment_categorical(const sss_segcat_args* a, int backward, void* stream);
 
+/* Executor timelines: the reference's `Executor.history` (spark_sched_sim/components/executor.py:21-44 - per executor the list of
+ * [t, job_id] pairs, t = the wall time at which the executor was released from job_id, None while it has not been; job_id -1 = the
+ * common pool), recorded by the simulator kernels themselves into caller-allocated rows OUTSIDE the state arena:
+ *   t_dev f64[num_envs][E][cap], job_dev i32[num_envs][E][cap], count_dev i32[num_envs][E]        (E = num_executors)
+ * Entry k < count - 1 holds its release time, the open (last) entry's time slot holds NaN. An episode initialisation (sss_reset
+ * for the envs of its mask, an auto-reset inside a step / rollout launch) restarts the env's rows at one open entry [NaN, -1]; an executor
+ * arriving at a job (spark_sched_sim.py:444-445) and a release to the common pool (:778-782) each close the open entry with the
+ * time of the event being handled and open the next one; a send (:627-629) writes nothing. count is the TRUE number of entries and
+ * may exceed cap: entries from index cap on are not stored (the release time of entry cap - 1 still is). Nothing outside the three
+ * arrays is ever written; envs skipped with SSS_SKIP_ENV keep their rows. (The two structures below have no typedef: C callers
+ * write `struct sss_timeline`.) Binding does not touch the rows: they describe an episode
+ * from its reset on (or from a caller's own [NaN, -1] / count 1 initialisation). tl == NULL unbinds; with nothing bound every
+ * output and the whole arena are byte for byte what they are without this feature. */
+struct sss_timeline {
+  double* t_dev;
+  int32_t* job_dev;
+  int32_t* count_dev;
+  int32_t cap; /* entries stored per executor, >= 1 */
+  int32_t pad_;
+};
+int sss_bind_timeline(sss_handle* h, const struct sss_timeline* tl);
+
+/* The bound timelines of n envs as Gantt frames (what the reference's renderer draws from the histories, components/renderer.py,
+ * spark_sched_sim.py:408-424; "rgb_array"): rgb_dev u8[n][height][width][3], env_ids_dev i32[n] or NULL (= envs 0 .. n - 1; an id
+ * outside [0, num_envs) leaves its frame untouched). A frame is defined by these rules, all in fp64, T = the env's wall time, J = the
+ * episode's job count: executor i owns pixel rows [i * rh, min((i + 1) * rh, height)), rh = ceil(height / E); column x shows the
+ * entry in force at tx = (x + 0.5) * (T / width) - the first entry k with tx < release_k, the open entry's release being +inf (so
+ * entries of zero length are never chosen); T <= 0: the open entry everywhere. Job j >= 0 is drawn in trunc(c1 + p * (c2 - c1)) per
+ * channel, p = (j + 1) / J, c1 = (0, 100, 255), c2 = (2, 247, 112); -1 is black. A row with count > cap is mid-grey (128, 128, 128)
+ * from the release time of its last stored entry on. Then every job with t_completed < T draws a red (255, 0, 0) column over the whole
+ * height at x = min(width - 1, floor(width * t_completed / T)). width, height in 1..16384. */
+struct sss_timeline_render_args {
+  const int32_t* env_ids_dev;
+  int32_t n, width, height, pad_;
+  uint8_t* rgb_dev;
+};
+int sss_timeline_render(sss_handle* h, const struct sss_timeline_render_args* a, void* stream);
+
 const char* sss_last_error(void);
 void sss_destroy(sss_handle* h);
 

@@ -163,6 +163,14 @@ class SssDiffretArgs(C.Structure):  # include/sss.h sss_diffret_args
                 ("sums_dev", C.c_void_p), ("out_dev", C.c_void_p), ("avg_dev", C.c_void_p)]
 
 
+class SssTimeline(C.Structure):  # include/sss.h sss_timeline
+    _fields_ = [("t_dev", C.c_void_p), ("job_dev", C.c_void_p), ("count_dev", C.c_void_p), ("cap", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SssTimelineRenderArgs(C.Structure):  # include/sss.h sss_timeline_render_args
+    _fields_ = [("env_ids_dev", C.c_void_p), ("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("pad_", C.c_int32), ("rgb_dev", C.c_void_p)]
+
+
 REWARD_WINDOW_CHUNK = 64  # include/sss.h SSS_REWARD_WINDOW_CHUNK
 
 
@@ -182,7 +190,7 @@ class SssArenaArgs(C.Structure):  # include/sss.h sss_arena_args
 
 EXPORTS = ["sss_query_dims", "sss_create", "sss_bind_buffers", "sss_reset", "sss_step", "sss_step_bounded", "sss_policy", "sss_rollout",
            "sss_decima_graph_build", "sss_decima_layer_lists", "sss_prefix_rows", "sss_decima_policy", "sss_decima_sample", "sss_gnn_launch",
-           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
+           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_bind_timeline", "sss_timeline_render", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
 POLICY_IDS = {"fair": 0, "fifo": 1, "hash": 2, "wfair": 3, "sjfcp": 4}
 WFAIR_ALPHA_RANGE = (-4, 4)  # sss_policy / sss_rollout: the weighted-fair exponent (param of policy 3)
 # the argument structures of include/sss.h and their mirrors here (Binding.check_abi)
@@ -194,6 +202,8 @@ ABI_STRUCTS = {"sss_cfg": SssCfg, "sss_dims": SssDims, "sss_buffers": SssBuffers
 # ... and the ones the header declares as `struct name { .. }; typedef struct name name;` (tests/test_abi.py pins the list of the
 # `} name;` typedefs above against a list of its own): checked at load in the same way
 ABI_TAGGED_STRUCTS = {"sss_reward_window_args": SssRewardWindowArgs, "sss_diffret_args": SssDiffretArgs}
+# ... and the ones it declares as `struct name { .. };` alone, without a typedef (tests pin both lists above against lists of their own)
+ABI_PLAIN_STRUCTS = {"sss_timeline": SssTimeline, "sss_timeline_render_args": SssTimelineRenderArgs}
 
 
 def load_library(path: str | None = None) -> C.CDLL:
@@ -242,6 +252,8 @@ class Binding:
         L.sss_sequence_baselines.argtypes = [C.POINTER(SssBaselineArgs), C.c_void_p]
         L.sss_reward_window_update.argtypes = [C.POINTER(SssRewardWindowArgs), C.c_void_p]
         L.sss_differential_returns.argtypes = [C.POINTER(SssDiffretArgs), C.c_void_p]
+        L.sss_bind_timeline.argtypes = [C.c_void_p, C.POINTER(SssTimeline)]
+        L.sss_timeline_render.argtypes = [C.c_void_p, C.POINTER(SssTimelineRenderArgs), C.c_void_p]
         L.sss_bit_lists.argtypes = [C.POINTER(SssBitListArgs), C.c_void_p]
         L.sss_arena_append.argtypes = [C.POINTER(SssArenaArgs), C.c_void_p]
         L.sss_rows_op.argtypes = [C.POINTER(SssRowsArgs), C.c_void_p]
@@ -255,7 +267,7 @@ class Binding:
     def check_abi(self) -> None:
         """every ctypes mirror above has the size the library was compiled with (include/sss.h sss_abi_sizeof): a binding and a
         library of different rounds fail here, not inside a kernel"""
-        bad = [(name, C.sizeof(cls), self.lib.sss_abi_sizeof(name.encode())) for name, cls in {**ABI_STRUCTS, **ABI_TAGGED_STRUCTS}.items()
+        bad = [(name, C.sizeof(cls), self.lib.sss_abi_sizeof(name.encode())) for name, cls in {**ABI_STRUCTS, **ABI_TAGGED_STRUCTS, **ABI_PLAIN_STRUCTS}.items()
                if C.sizeof(cls) != self.lib.sss_abi_sizeof(name.encode())]
         if bad:
             raise RuntimeError("binding / library mismatch (struct, sizeof in binding.py, sizeof in the library): " + ", ".join(map(str, bad)))

@@ -27,7 +27,8 @@ def sources() -> list[str]:
 OUT = osp.join(CSRC, "libsss_hip.so")
 # translation units: the C ABI with every kernel but the simulator's own, and the simulator kernels (sss_sim.h) - up to 64 executors, and
 # the wide instantiation (65..128 executors: the same source with -DSSS_WIDE, csrc/sss_wide.h)
-UNITS = ["sss_hip.hip", "sss_hip_sim.hip", "sss_hip_wide.hip"]
+# ... and both once more with -DSSS_TIMELINE: the kernels that record the executor timelines (csrc/sss_hip_sim_tl.hip, sss_hip_wide_tl.hip)
+UNITS = ["sss_hip.hip", "sss_hip_sim.hip", "sss_hip_wide.hip", "sss_hip_sim_tl.hip", "sss_hip_wide_tl.hip"]
 
 # -ffp-contract=off: f64 event times / rewards must round exactly as the reference's do (no FMA fusion)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function", "-I", CSRC]
@@ -39,7 +40,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 #   switch, so it stays off the other kernels, and tests/test_abi.py::test_simulator_kernels_do_not_spill holds the kernels' scratch
 #   sizes (tools/isa_counts.py) to what it buys: a toolchain that ignores or renames the flag fails that test instead of silently
 #   bringing the spills back.
-UNIT_FLAGS = {"sss_hip_sim.hip": ["-mllvm", "-disable-machine-licm"], "sss_hip_wide.hip": ["-mllvm", "-disable-machine-licm"]}
+UNIT_FLAGS = {u: ["-mllvm", "-disable-machine-licm"] for u in ("sss_hip_sim.hip", "sss_hip_wide.hip", "sss_hip_sim_tl.hip", "sss_hip_wide_tl.hip")}
 
 
 def hipcc() -> str:

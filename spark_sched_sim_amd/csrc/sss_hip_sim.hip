@@ -7,37 +7,53 @@
 #include "sss_sim.h"
 #include "sss_narrow.h"
 
+// the launchers of this unit: sss_narrow_launch_* - or, compiled with -DSSS_TIMELINE (csrc/sss_hip_sim_tl.hip), sss_narrow_tl_launch_* of the
+// recording kernels, which the plain ones hand over to when a timeline is bound (SSS_TL_DISPATCH)
+#ifdef SSS_TIMELINE
+#define SSS_LAUNCHER(name) sss_narrow_tl_launch_##name
+#define SSS_TL_DISPATCH(call)
+#else
+#define SSS_LAUNCHER(name) sss_narrow_launch_##name
+#define SSS_TL_DISPATCH(call) \
+  if (a.tl.t) return sss_narrow_tl_launch_##call
 int sss_narrow_hot_bytes() { return (int)sizeof(SssHot); }
 int sss_narrow_static_lds_bytes() { return SSS_STATIC_LDS_BYTES; }
+#endif
 
-int sss_narrow_launch_reset(const SssKernelArgs& a, int num_envs, const uint64_t* seeds, const double* tl, const uint8_t* mask, void* stream) {
-  hipLaunchKernelGGL(sss_reset_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, seeds, tl, mask);
+int SSS_LAUNCHER(reset)(const SssKernelArgs& a, int num_envs, const uint64_t* seeds, const double* tl, const uint8_t* mask, void* stream) {
+  SSS_TL_DISPATCH(reset(a, num_envs, seeds, tl, mask, stream));
+  hipLaunchKernelGGL(SSS_KNAME(sss_reset_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, seeds, tl, mask);
   return (int)hipGetLastError();
 }
-int sss_narrow_launch_step_bounded(const SssKernelArgs& a, int num_envs, const int32_t* stage_idx, const int32_t* num_exec, int auto_reset, uint64_t seed_stride,
+int SSS_LAUNCHER(step_bounded)(const SssKernelArgs& a, int num_envs, const int32_t* stage_idx, const int32_t* num_exec, int auto_reset, uint64_t seed_stride,
                                    int budget, uint8_t* ready, void* stream) {
-  hipLaunchKernelGGL(sss_step_bounded_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, stage_idx, num_exec, auto_reset, seed_stride,
+  SSS_TL_DISPATCH(step_bounded(a, num_envs, stage_idx, num_exec, auto_reset, seed_stride, budget, ready, stream));
+  hipLaunchKernelGGL(SSS_KNAME(sss_step_bounded_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, stage_idx, num_exec, auto_reset, seed_stride,
                      budget, ready);
   return (int)hipGetLastError();
 }
-int sss_narrow_launch_step(const SssKernelArgs& a, int num_envs, const int32_t* stage_idx, const int32_t* num_exec, int auto_reset, uint64_t seed_stride,
+int SSS_LAUNCHER(step)(const SssKernelArgs& a, int num_envs, const int32_t* stage_idx, const int32_t* num_exec, int auto_reset, uint64_t seed_stride,
                            void* stream) {
-  hipLaunchKernelGGL(sss_step_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, stage_idx, num_exec, auto_reset, seed_stride);
+  SSS_TL_DISPATCH(step(a, num_envs, stage_idx, num_exec, auto_reset, seed_stride, stream));
+  hipLaunchKernelGGL(SSS_KNAME(sss_step_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, stage_idx, num_exec, auto_reset, seed_stride);
   return (int)hipGetLastError();
 }
-int sss_narrow_launch_policy(const SssKernelArgs& a, int num_envs, int policy, int param, int32_t* stage_idx, int32_t* num_exec, void* stream) {
-  hipLaunchKernelGGL(sss_policy_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, stage_idx, num_exec);
+#ifndef SSS_TIMELINE
+int SSS_LAUNCHER(policy)(const SssKernelArgs& a, int num_envs, int policy, int param, int32_t* stage_idx, int32_t* num_exec, void* stream) {
+  hipLaunchKernelGGL(SSS_KNAME(sss_policy_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, stage_idx, num_exec);
   return (int)hipGetLastError();
 }
-int sss_narrow_launch_rollout(const SssKernelArgs& a, int num_envs, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride, void* stream) {
+#endif
+int SSS_LAUNCHER(rollout)(const SssKernelArgs& a, int num_envs, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride, void* stream) {
+  SSS_TL_DISPATCH(rollout(a, num_envs, policy, param, n_steps, auto_reset, seed_stride, stream));
   if (policy >= SSS_POLICY_WFAIR)  // weighted fair / SJF-CP: the kernel that has them (sss_sim.h)
-    hipLaunchKernelGGL(sss_rollout_heur_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, n_steps, auto_reset, seed_stride);
+    hipLaunchKernelGGL(SSS_KNAME(sss_rollout_heur_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, n_steps, auto_reset, seed_stride);
   else
-    hipLaunchKernelGGL(sss_rollout_kernel, dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, n_steps, auto_reset, seed_stride);
+    hipLaunchKernelGGL(SSS_KNAME(sss_rollout_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, n_steps, auto_reset, seed_stride);
   return (int)hipGetLastError();
 }
 
-#ifdef SSS_EVPROF3  // timing builds only (tools/debug/evprof3.py): reads and clears the scoped profiler's table
+#if defined(SSS_EVPROF3) && !defined(SSS_TIMELINE)  // timing builds only (tools/debug/evprof3.py): reads and clears the scoped profiler's table
 extern "C" int sss_debug_prof(unsigned long long* out64) {
   if (hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_prof3), sizeof(unsigned long long) * 96) != hipSuccess) return -1;
   static const unsigned long long zeros[96] = {0};

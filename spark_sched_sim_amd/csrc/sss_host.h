@@ -17,6 +17,7 @@
 #include "sss_rows.h"
 #include "sss_narrow.h"
 #include "sss_wide.h"
+#include "sss_timeline.h"  // the Gantt rasteriser and its launch (a kernel, or - without a device compiler - plain loops)
 
 // envs with more than 64 executors run on the wide instantiation of the kernels (sss_wide.h)
 static bool sss_is_wide(int num_executors) { return num_executors > 64; }
@@ -118,6 +119,7 @@ struct sss_handle {
   void* common_dev;
   SssParams P;
   SssPackDev pk;
+  SssTimeline tl;  // sss_bind_timeline; t == nullptr: nothing bound
 };
 
 static int sss_validate(const sss_cfg* cfg, const void* pack, size_t pack_bytes, int num_envs, SssPackHost* ph, int* J_cap) {
@@ -323,7 +325,7 @@ extern "C" int sss_abi_sizeof(const char* name) {
   SSS_ABI_SIZE(sss_bit_list_args) SSS_ABI_SIZE(sss_gnn_args) SSS_ABI_SIZE(sss_decima_policy_args) SSS_ABI_SIZE(sss_decima_sample_args)
   SSS_ABI_SIZE(sss_gnn_encode_args) SSS_ABI_SIZE(sss_collect_args) SSS_ABI_SIZE(sss_mlp_args) SSS_ABI_SIZE(sss_arena_array)
   SSS_ABI_SIZE(sss_arena_args) SSS_ABI_SIZE(sss_returns_args) SSS_ABI_SIZE(sss_baseline_args) SSS_ABI_SIZE(sss_rows_args) SSS_ABI_SIZE(sss_concat_part) SSS_ABI_SIZE(sss_concat_args) SSS_ABI_SIZE(sss_segcat_args)
-  SSS_ABI_SIZE(sss_reward_window_args) SSS_ABI_SIZE(sss_diffret_args)
+  SSS_ABI_SIZE(sss_reward_window_args) SSS_ABI_SIZE(sss_diffret_args) SSS_ABI_SIZE(sss_timeline) SSS_ABI_SIZE(sss_timeline_render_args)
 #undef SSS_ABI_SIZE
   return -1;
 }
@@ -340,6 +342,7 @@ extern "C" int sss_create(const sss_cfg* cfg, const void* pack, size_t pack_byte
   h->max_dag_depth = sss_pack_max_depth((const uint8_t*)pack, ph);
   sss_compute_layout(&h->L, num_envs, cfg->num_executors, J_cap, ph.s_max, ph.L, ph.max_edges_per_job, sss_hot_bytes(cfg->num_executors));
   memset(&h->B, 0, sizeof(h->B));
+  memset(&h->tl, 0, sizeof(h->tl));
 
   // pack + ziggurat tables -> device
   h->pack_dev = be_alloc(pack_bytes);
@@ -445,8 +448,40 @@ extern "C" int sss_bind_buffers(sss_handle* h, const sss_buffers* b) {
 
 static SssKernelArgs sss_args(const sss_handle* h) {
   SssKernelArgs a;
-  a.L = h->L, a.B = h->B, a.P = h->P, a.pk = h->pk;
+  a.L = h->L, a.B = h->B, a.P = h->P, a.pk = h->pk, a.tl = h->tl;
   return a;
+}
+
+extern "C" int sss_bind_timeline(sss_handle* h, const struct sss_timeline* tl) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!tl) {  // unbind
+    memset(&h->tl, 0, sizeof(h->tl));
+    return 0;
+  }
+  if (!tl->t_dev) return sss_fail(-40, "sss_bind_timeline: t_dev is NULL");
+  if (!tl->job_dev) return sss_fail(-40, "sss_bind_timeline: job_dev is NULL");
+  if (!tl->count_dev) return sss_fail(-40, "sss_bind_timeline: count_dev is NULL");
+  if (tl->cap < 1) return sss_fail(-40, "sss_bind_timeline: cap must be >= 1, got " + std::to_string(tl->cap));
+  h->tl.t = tl->t_dev, h->tl.job = tl->job_dev, h->tl.count = tl->count_dev, h->tl.cap = tl->cap, h->tl.pad_ = 0;
+  return 0;
+}
+
+extern "C" int sss_timeline_render(sss_handle* h, const struct sss_timeline_render_args* a, void* stream) {
+  if (!h || !a) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (!h->tl.t) return sss_fail(-41, "sss_timeline_render: no timeline is bound (sss_bind_timeline)");
+  if (a->n < 0 || a->n > h->L.num_envs) return sss_fail(-41, "sss_timeline_render: n must be in 0..num_envs");
+  if (a->width < 1 || a->width > 16384 || a->height < 1 || a->height > 16384) return sss_fail(-41, "sss_timeline_render: width and height must be in 1..16384");
+  if (a->n == 0) return 0;
+  if (!a->rgb_dev) return sss_fail(-41, "sss_timeline_render: rgb_dev is NULL");
+  SssRenderArgs r;
+  r.state = (const uint8_t*)h->B.state, r.env_stride = h->L.env_stride, r.off_t_completed = h->L.off_t_completed;
+  r.num_envs = h->L.num_envs, r.E = h->L.E, r.tl = h->tl, r.env_ids = a->env_ids_dev, r.n = a->n, r.W = a->width, r.H = a->height;
+  r.rh = (a->height + h->L.E - 1) / h->L.E, r.n_bands = (a->height + r.rh - 1) / r.rh, r.rgb = a->rgb_dev;
+  if ((int64_t)r.n * r.n_bands > 0x7FFFFFFF) return sss_fail(-41, "sss_timeline_render: too many (env, executor) bands for one launch");
+  BeDeviceGuard guard(h->device);
+  if (int rc = be_launch_timeline_render(r, stream)) return sss_fail(-30, std::string("timeline render launch failed: ") + be_error(rc));
+  return 0;
 }
 
 extern "C" int sss_reset(sss_handle* h, const uint64_t* seeds_dev, const double* time_limits_dev, const uint8_t* mask_dev, void* stream) {

@@ -239,12 +239,22 @@ struct SssBuffers {        // raw device pointers of torch-allocated tensors
   uint32_t gen, gen_pad;   // bumped by every sss_bind_buffers: rows written to other buffers do not count as written
 };
 
+// executor timelines (include/sss.h sss_bind_timeline): caller-allocated rows OUTSIDE the state arena, one per (env, executor).
+// t == nullptr: nothing is recorded. Entry k of a row is the reference's Executor.history[k] = [t, job_id] (executor.py:21-44).
+struct SssTimeline {
+  double* t;       // f64[B][E][cap] release time of the entry; NaN in the open (last) one
+  int32_t* job;    // i32[B][E][cap] job id, -1 = the common pool
+  int32_t* count;  // i32[B][E] entries so far - may exceed cap: entries from index cap on are counted, not stored
+  int32_t cap, pad_;
+};
+
 // the first argument of every simulator kernel (sss_sim.h reads it back from the kernel-argument segment)
 struct SssKernelArgs {
   SssLayout L;
   SssBuffers B;
   SssParams P;
   SssPackDev pk;
+  SssTimeline tl;
 };
 
 static inline int64_t sss_align(int64_t x, int64_t a) { return (x + a - 1) / a * a; }

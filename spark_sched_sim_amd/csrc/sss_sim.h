@@ -29,10 +29,21 @@
 // first event in the next round. The wave-uniform single-event paths, chunked fulfilment and the pair staging take executor ids
 // and list positions, not lanes, and only needed their tables and masks widened. -DSSS_NO_BATCH (either instantiation): every
 // event through the one-at-a-time handlers - the reference's control flow restated - for the byte-identity tests.
+// -DSSS_TIMELINE (either instantiation; csrc/sss_hip_sim_tl.hip, sss_hip_wide_tl.hip): the kernels that also record the executor
+// timelines (tl_append below), as SECOND instantiations under their own names. The ones without it are, instruction for
+// instruction, what they were before the recording existed - the launchers pick by whether a timeline is bound.
 #ifdef SSS_WIDE
+#ifdef SSS_TIMELINE
+#define SSS_KNAME(name) name##_wide_tl
+#else
 #define SSS_KNAME(name) name##_wide
+#endif
+#else
+#ifdef SSS_TIMELINE
+#define SSS_KNAME(name) name##_tl
 #else
 #define SSS_KNAME(name) name
+#endif
 #endif
 #include "../../include/sss.h"
 #include "sss_layout.h"
@@ -149,6 +160,45 @@ SSS_DEV Ctx ctx_make() {
 
 SSS_DEV void prof3_clear();
 SSS_DEV void ctx_init() { prof3_clear(); }
+
+// ---- executor timelines (SssTimeline: the reference's Executor.history, executor.py:21-44) ----
+// Recording is a compile-time switch of the kernels: on gfx950 the two functions below are empty unless the unit is compiled with
+// -DSSS_TIMELINE. With a run-time test on the bound pointer in the ONE form of each kernel, the fused rollout kernels went from
+// 0 / 8 to 6 / 11 spilled vector registers (narrow / wide; the budget tests/test_abi.py holds them to is 8) although the test is a
+// scalar branch - the address arithmetic of the appends lives across the event loop. The CPU emulator has no register budget:
+// one form, which looks at the pointer. The pointers ride in the kernel-argument segment. A row belongs to one executor
+// and is only ever written by the lane that handles that executor's event (lane 0 in the serial handlers, the executor's own
+// lane in the batches), with an ordering point between two events of one executor: plain loads and stores.
+#if defined(SSS_TIMELINE) || !defined(__HIP__)
+#define SSS_TL_RECORDS 1
+#else
+#define SSS_TL_RECORDS 0
+#endif
+// Executor.add_history(t, job) (executor.py:34-44): the open entry gets its release time, a new open entry [None, job] follows.
+// Entries from index cap on are counted only; every store is guarded by its own index, whatever the count buffer holds.
+SSS_DEV void tl_append(int e, double t, int job) {
+  if (!SSS_TL_RECORDS) return;
+  const SssKernelArgs* a = (const SssKernelArgs*)SSS_KERNARG_PTR();
+  double* const tt = a->tl.t;
+  if (!tt) return;
+  const int cap = a->tl.cap;
+  const size_t row = (size_t)wave_env() * (size_t)a->L.E + (size_t)e;
+  int32_t* const cnt = a->tl.count + row;
+  const int c = *cnt;
+  if (c >= 1 && c <= cap) tt[row * (size_t)cap + (size_t)(c - 1)] = t;
+  if (c >= 0 && c < cap) tt[row * (size_t)cap + (size_t)c] = __builtin_nan(""), a->tl.job[row * (size_t)cap + (size_t)c] = job;
+  *cnt = c + 1;
+}
+// Executor.__init__ (executor.py:25): history = [[None, -1]] - the row of executor e starts over (episode initialisation)
+SSS_DEV void tl_reset_row(int e) {
+  if (!SSS_TL_RECORDS) return;
+  const SssKernelArgs* a = (const SssKernelArgs*)SSS_KERNARG_PTR();
+  double* const tt = a->tl.t;
+  if (!tt) return;
+  const size_t row = (size_t)wave_env() * (size_t)a->L.E + (size_t)e;
+  tt[row * (size_t)a->tl.cap] = __builtin_nan(""), a->tl.job[row * (size_t)a->tl.cap] = -1;  // (cap >= 1: sss_bind_timeline)
+  a->tl.count[row] = 1;
+}
 
 #define SSS_SRC_ID 0  // which source file a failed check sits in: 0 = this file, 1.. = the parts below in include order
 #define H (g_hot.h)
@@ -679,6 +729,7 @@ SSS_DEV void run_policy(int policy, int param, int& stage_idx, int& num_exec) {
 }
 
 // writes one action per env into stage_idx / num_exec (for sss_step)
+#ifndef SSS_TIMELINE  // (reads the state only: there is no recording form of it)
 SSS_KERNEL void SSS_KNAME(sss_policy_kernel)(SssKernelArgs a, int policy, int param, int32_t* stage_idx, int32_t* num_exec) {
   int env = wave_env();
   uint8_t* base = (uint8_t*)a.B.state + (size_t)env * a.L.env_stride;
@@ -688,6 +739,7 @@ SSS_KERNEL void SSS_KNAME(sss_policy_kernel)(SssKernelArgs a, int policy, int pa
   run_policy(policy, param, si, ne);
   if (wave_lane() == 0) stage_idx[env] = si, num_exec[env] = ne;
 }
+#endif
 
 // n_steps x (policy -> step -> observe) per env in one launch; the env's hot block and job cache
 // stay in LDS in between. Every step still writes the full observation, as the reference's step() does.

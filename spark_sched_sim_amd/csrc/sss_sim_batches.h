@@ -365,6 +365,7 @@ SSS_DEV int batch_released_events(const FastCtx& f, int head) {
     if (detach) {  // JOB:86-89
       local_atomic_detach(jp, ex);
       g_hot.ex_job[ex] = -1, g_hot.ex_task_stage[ex] = -1;
+      if (type != RL_SEND) tl_append(ex, sl.t, -1);  // released to the common pool (ENV:778-782) at its own event's time; a send writes nothing (ENV:627-629)
     }
     if (rank == n - 1) {
       SssHdr& h = g_hot.h;
@@ -696,6 +697,7 @@ SSS_DEV int batch_arrival_events(const FastCtx& f, int head) {
     SssStage* stp = f.cstages + slot * f.SP + s;
     local_atomic_attach(jp, ex);  // JOB:81-84
     g_hot.ex_job[ex] = (int16_t)j;
+    tl_append(ex, sl.t, j);  // ENV:445, at its own event's time
     lane_atomic_add_u32((uint32_t*)stp + 1, 0u - STG_W1_MOVING_TO);  // moving_to-- (TRK:185-187)
     g_sc.fi_e[rank] = (uint8_t)ex, g_sc.fi_type[rank] = (uint8_t)type;
     g_sc.rl_old[rank] = jkey;

@@ -482,7 +482,7 @@ SSS_DEV bool resume_simulation(int budget = 0) {
           if (handled == 0) handled = tf ? lean_released(f, ex, t_win, info_win) : lean_arrival(f, ex, t_win, info_win);
 #endif
           // the event that completes a job: the executors parked in the job's pool are flushed with the whole wave first
-          if (handled == 0 && tf) preflush_completing_job(f, info_win);
+          if (handled == 0 && tf) preflush_completing_job(f, info_win, t_win);
         }
         if (handled > 0) continue;
         // nothing was touched: the popped event goes the one-at-a-time way, which is always right
@@ -600,6 +600,7 @@ SSS_DEV void do_reset(const SssLayout& L, uint64_t seed, double time_limit) {
     hot.ex_job[x] = -1;
     hot.ex_task_stage[x] = -1, hot.ex_executing[x] = 0;
     hot.c_src[x] = POOL_NONE, hot.c_dst[x] = POOL_NONE, hot.c_seq[x] = 0, hot.c_n[x] = 0;
+    if (x < g_c.E) tl_reset_row(x);
   }
   wave_sync();
   int J = hot.h.J;

@@ -85,6 +85,7 @@ SSS_DEV void handle_executor_arrival(int e, int j, int s) {  // ENV:440-450
   CHECK(g_hot.ex_task_stage[e] < 0);  // JOB:81-84
   v.job->local_mask = local_with(v.job->local_mask, e);
   g_hot.ex_job[e] = (int16_t)j;
+  tl_append(e, H.wall_time, j);  // ENV:445
   const int mv = (int)v.st[s].moving_to - 1;  // TRK:185-187
   CHECK(mv >= 0);
   v.st[s].moving_to = (uint8_t)mv;

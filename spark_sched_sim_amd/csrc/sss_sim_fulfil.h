@@ -172,7 +172,7 @@ SSS_DEV int fulfil_chunk(int c0, int n, int& serial_end) {
     } else {
       g_hot.ex_loc[e] = POOL_NONE;
       if (exj >= 0) {
-        g_hot.ex_job[e] = -1, g_hot.ex_task_stage[e] = -1;  // JOB:86-89
+        g_hot.ex_job[e] = -1, g_hot.ex_task_stage[e] = -1;  // JOB:86-89 (a send: no history entry, ENV:627-629)
 #ifndef SSS_WIDE  // (the wide instantiation keeps a count: popc64(m_send_att) below)
         lane_atomic_or_u64(&g_sc.fi_detach, bit64(e));
 #endif
@@ -356,7 +356,7 @@ SSS_DEV bool fulfil_common_wave(int from, int to) {
       for (int i = from; i < to; i++) {
         const int e = g_sc.fi_e[i];
         g_hot.ex_loc[e] = dstp;
-        if (dstp == POOL_COMMON) g_hot.ex_job[e] = -1, g_hot.ex_task_stage[e] = -1;  // JOB:86-89
+        if (dstp == POOL_COMMON) g_hot.ex_job[e] = -1, g_hot.ex_task_stage[e] = -1, tl_append(e, h.wall_time, -1);  // JOB:86-89, ENV:778-782
       }
       if (dstp == POOL_COMMON) local_group_detach(jp, moved);
     }

@@ -221,7 +221,7 @@ SSS_DEV void send_executor(int e, int j, int s) {  // ENV:617-637
   CHECK(!g_hot.ex_executing[e] && g_hot.ex_job[e] != j);
   trk_move_executor_to_pool(e, key_stage_pool(j, s), true);
   int oj = g_hot.ex_job[e];
-  if (oj >= 0) job_detach_executor(oj, e);
+  if (oj >= 0) job_detach_executor(oj, e);  // (ENV:627-629 writes no history: an executor in transit keeps showing its old job)
   push_event(e, H.wall_time + g_c.P.moving_delay, EV_EXECUTOR_READY, j, s);
 }
 
@@ -236,7 +236,7 @@ SSS_DEV void move_idle_executor(uint32_t src, int e) {
   if (s < 0 && !is_sat) return;
   uint32_t dst = is_sat ? POOL_COMMON : key_job_pool(j);
   trk_move_executor_to_pool(e, dst, false);
-  if (dst == POOL_COMMON) job_detach_executor(j, e);
+  if (dst == POOL_COMMON) job_detach_executor(j, e), tl_append(e, H.wall_time, -1);  // ENV:778-782
 }
 
 // set(id for id in pool.copy() if not executing) into sc->setB (ENV:714-728)
@@ -352,7 +352,7 @@ SSS_DEV void move_idle_executors_all(uint32_t src) {
     if (en < 2) continue;
     int e = (int)en - 2;
     trk_move_executor_to_pool(e, dst, false);
-    if (dst == POOL_COMMON) job_detach_executor(j, e);
+    if (dst == POOL_COMMON) job_detach_executor(j, e), tl_append(e, H.wall_time, -1);  // ENV:778-782
   }
 }
 

@@ -226,6 +226,7 @@ SSS_DEV int lean_released(const FastCtx& f, int ex, double t_ev, uint32_t info) 
     if (type == RL_SEND || type == RL_IDLE_COMMON) {      // JOB:86-89
       jp->local_mask = local_without(jp->local_mask, ex);
       g_hot.ex_job[ex] = -1, g_hot.ex_task_stage[ex] = -1;
+      if (type == RL_IDLE_COMMON) tl_append(ex, t_ev, -1);  // ENV:778-782; a send writes nothing (ENV:627-629)
     }
     // its event slot and the cache-slot references of the events' jobs
     SssEvSlot sl;
@@ -338,6 +339,7 @@ SSS_DEV int lean_arrival(const FastCtx& f, int ex, double t_ev, uint32_t info) {
     g_sc.events_this_step += 1;
     jp->local_mask = local_with(local, ex);  // JOB:81-84
     g_hot.ex_job[ex] = (int16_t)j;
+    tl_append(ex, t_ev, j);  // ENV:445
     SssStage t2 = st;
     t2.moving_to = (uint8_t)(t2.moving_to - 1);  // TRK:185-187
     SssEvSlot sl = g_hot.ev[ex];
@@ -375,7 +377,7 @@ SSS_DEV int lean_arrival(const FastCtx& f, int ex, double t_ev, uint32_t info) {
 // in list order; the handler then finds the job's pool empty and skips its own loop. Only called for a TASK_FINISHED event
 // of a cached job; does nothing unless that event completes the job.
 // ------------------------------------------------------------------------------------------
-SSS_DEV void preflush_completing_job(const FastCtx& f, uint32_t info) {
+SSS_DEV void preflush_completing_job(const FastCtx& f, uint32_t info, double t_ev) {
 #ifdef SSS_NO_BATCH
   return;
 #endif
@@ -419,6 +421,7 @@ SSS_DEV void preflush_completing_job(const FastCtx& f, uint32_t info) {
     for (int i = 0; i < m; i++) {
       const int e = g_sc.fi_e[i];
       g_hot.ex_loc[e] = POOL_COMMON, g_hot.ex_job[e] = -1, g_hot.ex_task_stage[e] = -1;
+      tl_append(e, t_ev, -1);  // ENV:778-782, at the time of the event that completes the job (the clock is set when it is handled)
     }
   }
   STAT(118, 1), STAT(119, m);

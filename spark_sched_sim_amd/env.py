@@ -34,21 +34,45 @@ class JobView:
         self.t_completed = t_completed
 
 
-class SparkSchedSimEnv(_Base):  # type: ignore[misc]
-    metadata = {"render_modes": [], "render_fps": 30}
+class ExecutorView:
+    """what the reference's renderer reads from `env.executors[i]` (spark_sched_sim.py:408-411): `id_` and `history`, the list
+    of [t, job_id] pairs of components/executor.py:21-44 (read from the device when asked for)"""
 
-    def __init__(self, env_cfg: dict[str, Any], device: str = "cuda:0", _lib=None) -> None:
-        if env_cfg.get("render_mode"):
-            raise ValueError("rendering is not available in the GPU build")  # pygame renderer is out of scope
+    def __init__(self, env: "SparkSchedSimEnv", id_: int):
+        self._env = env
+        self.id_ = id_
+
+    @property
+    def history(self) -> list[list]:
+        return self._env._histories()[self.id_]
+
+
+class SparkSchedSimEnv(_Base):  # type: ignore[misc]
+    metadata = {"render_modes": ["rgb_array"], "render_fps": 30}
+    RENDER_SIZE = (400, 300)  # width, height of an "rgb_array" frame
+    TIMELINE_CAP = 512        # history entries kept per executor (whole episodes of the usual configurations need ~100)
+
+    def __init__(self, env_cfg: dict[str, Any], device: str = "cuda:0", _lib=None, record_history: bool = True) -> None:
+        """`record_history=False` (not with a render mode): `Executor.history` is not kept - the env then runs the kernels
+        without recording and allocates no timeline rows; `executors[i].history` raises"""
+        render_mode = env_cfg.get("render_mode")
+        if render_mode and render_mode != "rgb_array":
+            raise ValueError("rendering is not available in the GPU build")  # the pygame window ("human") is out of scope
         self.num_executors: int = env_cfg["num_executors"]
         self.moving_delay = env_cfg["moving_delay"]
         self.beta: float = env_cfg.get("beta", 0)
         self.job_arrival_cap = env_cfg.get("job_arrival_cap")
-        self.render_mode = None
+        self.render_mode = render_mode or None
         from .spaces import make_action_space, make_observation_space
         self.action_space = make_action_space(self.num_executors)
         self.observation_space = make_observation_space(self.num_executors)
-        self._vec = VecSparkSchedSimEnv(env_cfg, 1, device=device, _lib=_lib)
+        self._vec = VecSparkSchedSimEnv({k: v for k, v in env_cfg.items() if k != "render_mode"}, 1, device=device, _lib=_lib)
+        if render_mode and not record_history:
+            raise ValueError("render_mode needs record_history=True")
+        if record_history:  # Executor.history is kept unless the caller opts out, as in the reference
+            self._vec.enable_timeline(self.TIMELINE_CAP)
+        self._hist_cache = None  # the histories as last fetched; a reset / step drops them
+        self.executors = [ExecutorView(self, i) for i in range(self.num_executors)]
         self._act_s = torch.zeros(1, dtype=torch.int32, device=self._vec.device)
         self._act_n = torch.ones(1, dtype=torch.int32, device=self._vec.device)
 
@@ -58,6 +82,7 @@ class SparkSchedSimEnv(_Base):  # type: ignore[misc]
         time_limit = (options or {}).get("time_limit", np.inf)
         if time_limit is np.inf and not self.job_arrival_cap:
             raise ValueError("must either have a limit on job arrivals or time.")
+        self._hist_cache = None
         self._vec.reset(seed=None if seed is None else [seed], options=options)
         self._raise()
         self.job_arrival_cap = self._vec.header(0)["J"]  # reference overwrites it (spark_sched_sim.py:156)
@@ -72,6 +97,7 @@ class SparkSchedSimEnv(_Base):  # type: ignore[misc]
                 raise ValueError("invalid action: does not belong to the action space")
         self._act_s[0] = int(action["stage_idx"])
         self._act_n[0] = int(action["num_exec"])
+        self._hist_cache = None
         self._vec.step_async(self._act_s, self._act_n)
         self._raise()
         o = self._vec.obs_i32[0].cpu().numpy()
@@ -83,6 +109,20 @@ class SparkSchedSimEnv(_Base):  # type: ignore[misc]
         self.action_space["stage_idx"].n = len(obs["dag_batch"].nodes) + 1  # spark_sched_sim.py:403-404
         self.observation_space["dag_ptr"].feature_space.n = len(obs["dag_batch"].nodes) + 1
         return obs
+
+    def _histories(self) -> list[list[list]]:
+        """every executor's history, fetched from the device once per step: `[e.history for e in env.executors]`
+        (spark_sched_sim.py:411) is one copy, not one per executor"""
+        if self._hist_cache is None:
+            self._hist_cache = self._vec.timeline(0)
+        return self._hist_cache
+
+    def render(self):
+        """an H x W x 3 uint8 frame of the executors' Gantt chart (render_mode "rgb_array"; VecSparkSchedSimEnv.render), else None"""
+        if self.render_mode != "rgb_array":
+            return None
+        w, h = self.RENDER_SIZE
+        return self._vec.render([0], width=w, height=h)[0].cpu().numpy()
 
     def close(self) -> None:
         self._vec.close()

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import workload
-from .binding import ERROR_NAMES, POLICY_IDS, WFAIR_ALPHA_RANGE, Binding, SssBuffers, SssCfg, SssDecimaGraph, SssDecimaLists, device_of
+from .binding import (ERROR_NAMES, POLICY_IDS, WFAIR_ALPHA_RANGE, Binding, SssBuffers, SssCfg, SssDecimaGraph, SssDecimaLists, SssTimeline,
+                      SssTimelineRenderArgs, device_of)
 
 OBS_FIELDS = ("n_nodes", "n_edges", "n_jobs", "n_schedulable", "num_committable_execs", "source_job_idx",
               "terminated", "err")
@@ -155,6 +156,7 @@ class VecSparkSchedSimEnv:
                           self.dag_ptr.data_ptr(), self.exec_supplies.data_ptr(), self.obs_i32.data_ptr(),
                           self.obs_f64.data_ptr())
         self._b.check(self._b.lib.sss_bind_buffers(self._h, C.byref(bufs)))
+        self._bind_timeline()  # (a recording that is on stays on)
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
@@ -250,6 +252,74 @@ class VecSparkSchedSimEnv:
         if self._never is None or self._never.shape != terminated.shape:
             self._never = torch.zeros_like(terminated)  # (truncation is the time-limit wrapper's business: always False here; shared, read-only)
         return obs, f64[:, 0], terminated, self._never, {"wall_time": f64[:, 1], "err": i32[:, 1]}
+
+    # ---- executor timelines (the reference's Executor.history) and Gantt frames -----------------
+
+    def _bind_timeline(self) -> None:
+        tl = getattr(self, "_timeline", None)
+        if tl is None:
+            self._b.check(self._b.lib.sss_bind_timeline(self._h, None))
+            return
+        t, job, count = tl
+        a = SssTimeline(t.data_ptr(), job.data_ptr(), count.data_ptr(), t.shape[2], 0)
+        self._b.check(self._b.lib.sss_bind_timeline(self._h, C.byref(a)))
+
+    def enable_timeline(self, cap: int = 256) -> None:
+        """starts recording every executor's history on the device (include/sss.h sss_bind_timeline; the reference's
+        `Executor.history`, components/executor.py:21-44): `cap` entries are stored per executor, further ones are only counted.
+        The rows start as after a reset - one open entry [None, -1] - so a recording describes an episode when it is enabled
+        before the episode's `reset`; every reset (also an auto-reset inside a launch) restarts the env's rows."""
+        cap = int(cap)
+        if cap < 1:
+            raise ValueError(f"enable_timeline: cap must be >= 1, got {cap}")
+        B, E, dev = self.num_envs, self.num_executors, self.device
+        t = torch.full((B, E, cap), float("nan"), dtype=torch.float64, device=dev)
+        job = torch.full((B, E, cap), -1, dtype=torch.int32, device=dev)
+        count = torch.ones((B, E), dtype=torch.int32, device=dev)
+        self._timeline = (t, job, count)
+        self._bind_timeline()
+
+    def disable_timeline(self) -> None:
+        self._timeline = None
+        self._bind_timeline()
+
+    def timeline_arrays(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(t f64[B, E, cap], job i32[B, E, cap], count i32[B, E]) - the device tensors the kernels write. Entry k < count - 1 holds
+        its release time, the open entry NaN; count is the true number of entries and may exceed cap (the rest is not stored)"""
+        if getattr(self, "_timeline", None) is None:
+            raise RuntimeError("no timeline is being recorded: call enable_timeline() first")
+        return self._timeline
+
+    def timeline(self, i: int) -> list[list[list]]:
+        """env i's histories in the reference's shape: per executor the list of [t, job_id] pairs, None in the open entry's t
+        (one device->host copy). Raises when an executor has more entries than the capacity holds."""
+        t, job, count = self.timeline_arrays()
+        cap = t.shape[2]
+        cnt = count[i].cpu().numpy()
+        if int(cnt.max()) > cap:
+            raise RuntimeError(f"timeline of env {i} overflowed: executor {int(cnt.argmax())} has {int(cnt.max())} entries, the capacity is {cap}; "
+                               f"enable_timeline(cap={int(cnt.max())}) would have held the episode")
+        tt, jj = t[i].cpu().numpy(), job[i].cpu().numpy()
+        return [[[None if k == n - 1 else float(tt[e, k]), int(jj[e, k])] for k in range(n)] for e, n in enumerate(cnt.tolist())]
+
+    def render(self, env_ids=None, width: int = 400, height: int = 300) -> torch.Tensor:
+        """Gantt frames of the recorded timelines, uint8 [n, height, width, 3] on the device, written by one kernel (include/sss.h
+        sss_timeline_render, where the frame is defined): one band of rows per executor coloured by the job it belongs to over
+        [0, wall_time), black = the common pool, red columns = job completions, grey = beyond the recording's capacity.
+        `env_ids`: the envs to draw (any sequence / tensor of indices), None = all."""
+        self.timeline_arrays()
+        dev = self.device
+        if env_ids is None:
+            ids, n = None, self.num_envs
+        else:
+            ids = torch.as_tensor(env_ids, dtype=torch.int32).reshape(-1).to(dev).contiguous()
+            n = int(ids.numel())
+            if n and (int(ids.min()) < 0 or int(ids.max()) >= self.num_envs):
+                raise IndexError("render: env id out of range")
+        rgb = torch.empty((n, int(height), int(width), 3), dtype=torch.uint8, device=dev)
+        a = SssTimelineRenderArgs(ids.data_ptr() if ids is not None and n else None, n, int(width), int(height), 0, rgb.data_ptr() if n else None)
+        self._b.check(self._b.lib.sss_timeline_render(self._h, C.byref(a), self._stream()))
+        return rgb
 
     # ---- on-device policies and fused rollouts ---------------------------------------------
 
@@ -581,6 +651,9 @@ class VecSparkSchedSimEnv:
         return tot
 
 
+# byte offset of SssHot::ex_job (i16 per executor) inside an env's arena block, by the kernels' executor capacity (csrc/sss_layout.h:
+# 64 up to 64 executors, 128 in the wide instantiation); pinned by tests/test_emu_timeline.py against the header compiled with g++
+HOT_EX_JOB_OFF = {64: 320 + 64 * 16 + 64 * 4, 128: 320 + 128 * 16 + 128 * 4}
 # byte offsets inside SssHdr (csrc/sss_layout.h); pinned by tests/test_abi.py against the header compiled with gcc
 HDR_PROF = 208  # uint64 prof[5]: shader-clock ticks in slow-path handlers, action + fulfil, event loop, reward, observe
 HDR_OFF = {"wall_time": 40, "time_limit": 48, "seed": 56, "n_steps": 64, "n_events": 72, "model_bytes": 80,
