@@ -1,6 +1,6 @@
 """Builds the HIP extension in-tree: spark_sched_sim_amd/csrc/libsss_hip.so (gfx950).
 
-    python -m spark_sched_sim_amd.build            # build if sources are newer than the .so
+    python -m spark_sched_sim_amd.build            # build if the .so was not built from these sources
     python -m spark_sched_sim_amd.build --force
 """
 from __future__ import annotations
@@ -50,16 +50,31 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found (ROCm toolchain required to build the HIP extension)")
 
 
-def needs_build(out: str = OUT) -> bool:
-    if not osp.exists(out):
+def source_digest(extra_flags: tuple[str, ...] = ()) -> str:
+    """sha256 over `extra_flags` and the contents of `sources()` (the compiler flags are in this file)"""
+    import hashlib
+    h = hashlib.sha256(repr(tuple(extra_flags)).encode())
+    for s in sources():
+        with open(s, "rb") as f:
+            h.update(osp.basename(s).encode() + b"\0" + f.read())
+    return h.hexdigest()
+
+
+def needs_build(out: str = OUT, extra_flags: tuple[str, ...] = ()) -> bool:
+    """the library is missing, or was not built from these sources with these flags: `out`.stamp keeps the digest of what it was
+    built from. (Not modification times: a library that came from another checkout - an older round's tests/_build - can be newer
+    than every source and still have another ABI.)"""
+    try:
+        with open(out + ".stamp") as f:
+            return not osp.exists(out) or f.read().strip() != source_digest(extra_flags)
+    except OSError:
         return True
-    t = osp.getmtime(out)
-    return any(osp.getmtime(s) > t for s in sources())
 
 
 def build(force: bool = False, verbose: bool = False, out: str = OUT, extra_flags: tuple[str, ...] = ()) -> str:
     """compiles the translation units side by side, links them into `out`. `extra_flags`: test builds only (tests/gpu_variant.py)"""
-    if force or needs_build(out):
+    if force or needs_build(out, extra_flags):
+        digest = source_digest(extra_flags)  # (of what the compiler is about to read)
         from concurrent.futures import ThreadPoolExecutor
         objdir = osp.join(osp.dirname(out), "build", osp.splitext(osp.basename(out))[0])
         os.makedirs(objdir, exist_ok=True)
@@ -79,6 +94,8 @@ def build(force: bool = False, verbose: bool = False, out: str = OUT, extra_flag
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True, cwd=CSRC)
+        with open(out + ".stamp", "w") as f:
+            f.write(digest + "\n")
     return out
 
 

@@ -15,12 +15,14 @@ steps are always a prefix). Observation (t, b) is observation id t*B + b of `gra
 from __future__ import annotations
 
 import contextlib
+import ctypes
 from dataclasses import dataclass, field
 from typing import Any, Callable, Sequence
 
 import numpy as np
 import torch
 
+from .binding import ERROR_NAMES, SssCollectArgs, device_of
 from .decima import concat_graphs, select_observations
 from .wrappers import VecStochasticTimeLimit
 
@@ -142,9 +144,6 @@ class GraphArena:
         self._args = None
 
     def append(self, g: dict[str, Any], rows_hint: int = 0) -> None:
-        import ctypes
-
-        from .binding import device_of
         key = tuple(g[name].data_ptr() for name, *_ in self.ARRAYS) + (g["totals_dev"].data_ptr(),)
         if self._args is None or self._args[1] != key:
             self._build_args(g)
@@ -171,6 +170,45 @@ class GraphArena:
         return out
 
 
+class _Collection:
+    """What one collection keeps between its steps: the envs' state (who takes part, their clocks, who failed), the record -
+    [T_cap, B] arrays that grow geometrically, row t written by step t's `sss_collect_step` phase 1 together with row t of the
+    [T_cap, 8] flags - and what the host has learnt of the steps so far."""
+
+    SPEC = (("active", torch.uint8), ("t_before", torch.float64), ("t_after", torch.float64), ("rewards", torch.float64), ("stage_sel", torch.int64),
+            ("job_idx", torch.int64), ("exec_sel", torch.int64), ("lgprobs", torch.float32), ("resets", torch.uint8))  # (the order of sss_collect_args' rec_*)
+
+    def __init__(self, asynchronous: bool, duration: float, wall: torch.Tensor, cap: int = 1024):
+        B, dev = wall.shape[0], wall.device
+        self.asynchronous, self.duration, self.wall = asynchronous, duration, wall
+        self.elapsed = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.active = torch.ones(B, dtype=torch.uint8, device=dev)  # (bool view for the graph kernel and the caller's policy)
+        self.pending = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.cap = cap
+        self.rows = {name: torch.zeros((cap, B), dtype=dt, device=dev) for name, dt in self.SPEC}
+        self.flags = torch.zeros((cap, 8), dtype=torch.int32, device=dev)
+        self.alive = B > 0   # somebody takes part in the next step
+        self.n_kept = 0      # steps that are part of the record
+        self.n_lockstep = 0  # steps a loop that reads every step's flags before issuing the next would have issued (a dropped last step included)
+        self.n_failed = 0
+
+    def grow(self) -> None:
+        for name, a in self.rows.items():
+            self.rows[name] = torch.cat([a, torch.zeros_like(a)])
+        self.flags = torch.cat([self.flags, torch.zeros_like(self.flags)])
+        self.cap *= 2
+
+    def row_pointers(self, t: int) -> tuple[int, ...]:
+        """the tail of `sss_collect_args` for step t: the record's arrays, then the step's flags"""
+        return (*(a.data_ptr() for a in self.rows.values()), self.flags[t].data_ptr())
+
+    def fields(self) -> dict[str, torch.Tensor]:
+        """the kept rows as `Rollouts` fields"""
+        out = {name: a[: self.n_kept] for name, a in self.rows.items()}
+        out["active"], out["resets"] = out["active"].view(torch.bool), out["resets"].view(torch.bool)
+        return out
+
+
 class RolloutCollector:
     """the reference's `RolloutWorkerSync` / `RolloutWorkerAsync` loops for all envs at once.
 
@@ -183,14 +221,9 @@ class RolloutCollector:
     SSS_SKIP_ENV until the others catch up."""
 
     def __init__(self, env, mean_time_limit: float, base_seeds: Sequence[int], seed_step: int, num_executors: int,
-                 policy=None, act_fn: ActFn | None = None, generator: torch.Generator | None = None, on_env_error: str = "raise", groups: int = 1,
+                 policy=None, act_fn: ActFn | None = None, generator: torch.Generator | None = None, on_env_error: str = "raise",
                  record_on_device: bool = True):
-        """groups: the envs are split into that many groups that take their steps alternately, each on its own HIP stream (the
-        idea: while one group's step launch waits for its slowest env the other group's policy kernels have the device). The
-        record and the results per env are the same as with one group; on one MI355X it is SLOWER (every launch of the policy
-        pass is latency-bound and costs a half-size group as much as the whole batch: 0.88 -> 1.84 ms per row of the record
-        with two groups, profiles/r03_ppo.md), so 1 is the default.
-        record_on_device: synchronous collection with the default policy sampling keeps the host out of the loop - the step's
+        """record_on_device: synchronous collection with the default policy sampling keeps the host out of the loop - the step's
         graph stays in the env's capacity buffers with its sizes on the device, `GraphArena` appends it to the record there, and
         the flags of a step are read a few steps late (the steps enqueued in between find every env frozen when the collection
         turns out to be over). The record is the same; False reads the sizes and the flags every step (two waits per step).
@@ -198,9 +231,10 @@ class RolloutCollector:
         reference's `[step]` assertion (spark_sched_sim.py:212-215), which valid Decima actions can
         trigger (tests/golden/stall_case.json). "raise" = the reference's behaviour (the worker
         aborts, the trainer stops, rollout_worker.py:110-112 / trainer.py:117-124); "truncate" = the
-        rollout ends before the failing step and training goes on (`env_errors` counts them)."""
+        rollout ends before the failing step and training goes on (`env_errors` counts them).
+        (All envs take their steps together on one stream. Alternating groups of envs on streams of their own were measured
+        slower on one MI355X - 1.84 ms per row of the record with two groups against 0.88 ms, profiles/r03_ppo.md - and removed.)"""
         assert on_env_error in ("raise", "truncate")
-        self.groups = max(1, min(int(groups), env.num_envs))
         self.record_on_device = bool(record_on_device)
         self._arena_sizes = None  # the previous collection's graph sizes: the next arena's starting capacity
         self.on_env_error = on_env_error
@@ -218,7 +252,7 @@ class RolloutCollector:
         if policy is not None:
             policy.bind_kernels(env._b)  # inference on the fused GNN kernels; training stays on autograd
         self.act_fn = act_fn
-        self._obs = None
+        self._in_episodes = False  # the envs are inside their episodes (async: the next collection goes on from there)
         self._wall = None
         self._pending_reset = None
 
@@ -226,236 +260,170 @@ class RolloutCollector:
     def seeds(self) -> np.ndarray:
         return self.base_seeds + self.seed_step * self.reset_count
 
-    def _reset(self, mask: torch.Tensor | None = None):
-        obs, _ = self.tl_env.reset(seed=[int(s) for s in self.seeds], mask=mask)
+    def _reset(self, mask: torch.Tensor | None = None) -> None:
+        self.tl_env.reset(seed=[int(s) for s in self.seeds], mask=mask)
         self.reset_count += 1 if mask is None else mask.cpu().numpy().astype(np.int64)
-        return obs
 
     def _stats(self) -> dict[str, np.ndarray]:
         """rollout_worker.py:122-130 for every env"""
         return {k: v.cpu().numpy() for k, v in self.env.rollout_stats().items()}
 
-    def _loop(self, asynchronous: bool, duration: float, with_stats: bool) -> Rollouts:
-        """Both worker loops. Per step of a group of envs: the compact graph of its active envs' observations (recorded),
-        the policy's sample, `sss_collect_step` phase 0 (actions; the other groups' envs skip), `sss_step`,
-        `sss_collect_step` phase 1 (time limit, who failed / finished / goes on, the step's row of the record, the envs'
-        clocks). The flags the control flow needs are read when the group's NEXT step is about to be enqueued - by then the
-        other groups' work has been enqueued behind it (one device->host read per group and step, plus the graph totals).
-        The record lives in [T_cap, B] device arrays that grow geometrically."""
-        import contextlib
-        import ctypes
+    def _issue(self, col: _Collection, t: int, stage_idx: torch.Tensor, num_exec: torch.Tensor, arena: GraphArena | None = None) -> dict[str, Any]:
+        """Enqueues step t: the compact graph of the active envs' observations (recorded: returned, or appended to `arena` with
+        its sizes left on the device), the policy's sample, `sss_collect_step` phase 0 (the env's actions, into `stage_idx` /
+        `num_exec`), `sss_step`, `sss_collect_step` phase 1 (time limit, who failed / finished / goes on, row t of the record
+        and of the flags, the envs' clocks). Waits for nothing but what the graph and the policy wait for."""
+        env, dev = self.env, self.env.device
+        if t == col.cap:
+            col.grow()
+        act_b = col.active.view(torch.bool)
+        g = env.decima_graph(act_b) if arena is None else env.decima_graph_on_device(act_b)
+        a = self.act_fn(g, self.step_counts) if self.act_fn is not None else self.policy.act(g, self.generator)
+        if arena is not None:
+            hint = g["totals_hint"].tolist()
+            arena.append(g, rows_hint=max(5 * hint[0], hint[1], hint[2], env.num_envs) if hint[0] >= 0 else 0)
+        sel = [a[n] if a[n].dtype == torch.int64 and a[n].is_contiguous() else a[n].to(torch.int64).contiguous() for n in ("stage_sel", "job_idx", "exec_sel")]
+        lg = a["lgprob"] if a["lgprob"].dtype == torch.float32 and a["lgprob"].is_contiguous() else a["lgprob"].float().contiguous()
+        c = SssCollectArgs(env.num_envs, int(col.asynchronous), t, float(col.duration), env.obs_f64.data_ptr(), env.obs_i32.data_ptr(), env.obs_i32.stride(0),
+                           self.tl_env.time_limit.data_ptr(), col.active.data_ptr(), col.wall.data_ptr(), col.elapsed.data_ptr(), self.step_counts.data_ptr(),
+                           col.pending.data_ptr(), sel[0].data_ptr(), sel[1].data_ptr(), sel[2].data_ptr(), lg.data_ptr(), stage_idx.data_ptr(), num_exec.data_ptr(),
+                           *col.row_pointers(t))
+        stream = env._stream()
+        with device_of(dev):
+            env._b.check(env._b.lib.sss_collect_step(ctypes.byref(c), 0, stream))
+        env.step_async(stage_idx, num_exec)
+        with device_of(dev):
+            env._b.check(env._b.lib.sss_collect_step(ctypes.byref(c), 1, stream))
+        return g
 
-        from .binding import SssCollectArgs, device_of
-        env, dev, B, G = self.env, self.env.device, self.env.num_envs, self.groups
-        if not asynchronous or self._obs is None:
-            self._obs = self._reset()
+    def _outcome(self, col: _Collection, t: int, flags: Sequence[int], stage_idx: torch.Tensor, num_exec: torch.Tensor) -> None:
+        """what became of step t, from the first five of its flags (the step has finished): an env's error raises or truncates,
+        the step is counted as kept unless it failed for every env left, async resets, whether anybody is left (`col.alive`)"""
+        any_bad, any_done, any_left, bad_env, any_recorded = flags
+        col.n_lockstep = t + 1
+        if any_bad:
+            n_bad = int(col.pending.sum()) - col.n_failed
+            col.n_failed += n_bad
+            self.env_errors += n_bad
+            if self.on_env_error == "raise":
+                b = bad_env - 1
+                code = int(self.env.obs_i32[b, 7])
+                err = RuntimeError(f"env {b} (seed {int(self.seeds[b] - self.seed_step)}), rollout step {t}: "
+                                   f"{ERROR_NAMES.get(code, code)}; action stage_idx={int(stage_idx[b])} num_exec={int(num_exec[b])}")
+                # what a bug report needs: the env's seed, time limit and action history
+                err.case = {"seed": int(self.seeds[b] - self.seed_step), "time_limit": float(self.tl_env.time_limit[b]), "code": code,
+                            "stage_idx": [int(x) for x in col.rows["stage_sel"][:t, b]] + [int(stage_idx[b])],
+                            "num_exec": [int(x) + 1 for x in col.rows["exec_sel"][:t, b]] + [int(num_exec[b])]}
+                raise err
+            # truncate: the failing step is not recorded and the env sits out the rest of this
+            # collection (async: it starts its next episode at the next collection)
+            if not any_recorded:
+                col.alive = False
+                return
+        col.n_kept = t + 1
+        if col.asynchronous and any_done:
+            self._reset(mask=col.rows["resets"][t].view(torch.bool))
+        col.alive = bool(any_left)
+
+    def _collect_waiting(self, col: _Collection) -> dict[str, Any]:
+        """The loop that waits: the graph's sizes and the flags are read after every step (two device->host reads per step),
+        the kept steps' graphs are concatenated at the end."""
+        B, dev = self.env.num_envs, self.env.device
+        acts = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        graphs = []
+        t = 0
+        while col.alive:
+            g = self._issue(col, t, *acts)
+            self._outcome(col, t, col.flags[t, :5].tolist(), *acts)
+            if col.n_kept == t + 1:
+                graphs.append(g)
+            t += 1
+        return concat_graphs(graphs)
+
+    def _collect_ahead(self, col: _Collection) -> dict[str, Any]:
+        """The loop that runs ahead (see __init__, record_on_device): the graphs go to a `GraphArena` on the device, what the
+        host wants of a step - its flags and the arena's cursors after it - lands in pinned rings of R slots, and the host looks
+        at a step when it has finished or when LAG steps have been enqueued behind it (one pinned-ring read per step)."""
+        env, dev, B = self.env, self.env.device, self.env.num_envs
+        LAG, R = 4, 8
+        cuda = dev.type == "cuda"
+        pin = (lambda x: x.pin_memory()) if cuda else (lambda x: x)
+        cap0 = None
+        if self._arena_sizes:
+            d = env.dims
+            step_max = (B * d.node_cap, B * d.edge_cap, B * d.job_cap, B)
+            cap0 = [int(1.1 * c) + (LAG + 4) * m for c, m in zip(self._arena_sizes, step_max)]
+        arena = GraphArena(env, cap0)
+        ring_flags, ring_cur = pin(torch.zeros((R, 8), dtype=torch.int32)), pin(torch.zeros((R, 8), dtype=torch.int64))
+        ring_acts = [(torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)) for _ in range(R)]
+        ring_ev = [torch.cuda.Event() for _ in range(R)] if cuda else None
+        calls0 = getattr(self.policy, "_calls", 0)
+        late: list[int] = []  # steps enqueued whose flags have not been looked at, oldest first
+
+        def take_late() -> None:
+            """the oldest enqueued step's flags (waits for that step if it has not finished)"""
+            t = late.pop(0)
+            if ring_ev is not None:
+                ring_ev[t % R].synchronize()
+            cursors = ring_cur[t % R].tolist()  # (ring_cur[.., 4] = steps appended: which step the cursors are of)
+            self._outcome(col, t, ring_flags[t % R, :5].tolist(), *ring_acts[t % R])
+            if col.n_kept == t + 1:  # (a last step that failed for every env left is dropped: the arena's record ends before it)
+                arena.note(cursors, t + 1)
+
+        def drain_all() -> None:
+            while late and col.alive:
+                take_late()
+
+        t = 0
+        while col.alive:
+            # look at the steps that have finished, and never run more than LAG steps ahead of the flags
+            while late and col.alive and (len(late) >= LAG or ring_ev is None or ring_ev[late[0] % R].query()):
+                take_late()
+            if col.alive:
+                arena.ensure(drain_all)
+                self._issue(col, t, *ring_acts[t % R], arena=arena)
+                ring_flags[t % R].copy_(col.flags[t], non_blocking=True)
+                ring_cur[t % R].copy_(arena.cursor, non_blocking=True)
+                if ring_ev is not None:
+                    ring_ev[t % R].record(torch.cuda.current_stream(dev))
+                late.append(t)
+                t += 1
+                if ring_ev is None:
+                    take_late()
+        if cuda:
+            torch.cuda.current_stream(dev).synchronize()
+        graph = arena.finish(col.n_kept, arena.seen)  # (the steps enqueued behind the last kept one are dropped)
+        # the steps enqueued behind the last one found every env frozen, but each took a draw counter of the policy's sampling
+        # stream (decima._sample_kernels): hand them back, so that the next collection draws what it would have drawn - the loop
+        # that waits for every step's flags has issued n_lockstep steps (a last step that failed for every env left took its
+        # counter too, although it is not part of the record)
+        if hasattr(self.policy, "_calls"):
+            self.policy._calls = calls0 + col.n_lockstep
+        self._arena_sizes = [int(graph["x"].shape[0]), int(graph["src"].numel()), int(graph["job_obs"].numel()), col.n_kept * B]
+        return graph
+
+    def _loop(self, asynchronous: bool, duration: float, with_stats: bool) -> Rollouts:
+        """Both worker loops: the collection's set-up (sync: every env starts an episode; async: the envs go on where the last
+        collection left them, those that failed in it start a new episode), one of the two drivers, the record as `Rollouts`."""
+        env, dev, B = self.env, self.env.device, self.env.num_envs
+        if not asynchronous or not self._in_episodes:
+            self._reset()
+            self._in_episodes = True
             self._wall = torch.zeros(B, dtype=torch.float64, device=dev)
         wall = self._wall
         if asynchronous and self._pending_reset is not None:
             self._reset(mask=self._pending_reset)
             wall = torch.where(self._pending_reset, torch.zeros_like(wall), wall)
         self._pending_reset = None
-        wall = wall.clone()
-        elapsed = torch.zeros(B, dtype=torch.float64, device=dev)
-        active = torch.ones(B, dtype=torch.uint8, device=dev)  # (bool view for the graph kernel and the caller's policy)
-        pending = torch.zeros(B, dtype=torch.uint8, device=dev)
-        spec = (("active", torch.uint8), ("t_before", torch.float64), ("t_after", torch.float64), ("rewards", torch.float64), ("stage_sel", torch.int64),
-                ("job_idx", torch.int64), ("exec_sel", torch.int64), ("lgprobs", torch.float32), ("resets", torch.uint8))
-        cap = 1024
-        rec = {k: torch.zeros((cap, B), dtype=dt, device=dev) for k, dt in spec}  # (zeros: rows a group never reaches read as inactive)
-        flags = torch.zeros((cap, G, 8), dtype=torch.int32, device=dev)
-        group_of = (torch.arange(B, device=dev) * G) // max(B, 1)
-        member = [(group_of == k).to(torch.uint8) for k in range(G)] if G > 1 else [None]
-        member_b = [m.view(torch.bool) if m is not None else None for m in member]
-        use_streams = G > 1 and dev.type == "cuda"
-        main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        # the groups' streams are created once per collector: the per-stream work buffers of the graph / encoder calls
-        # (vec_env._layer_scratch, decima._enc_scratch) are keyed by stream and would pile up with fresh streams per call
-        if use_streams and len(getattr(self, "_streams", ())) != G:
-            self._streams = [torch.cuda.Stream(device=dev) for _ in range(G)]
-        streams = list(self._streams) if use_streams else [None] * G
-        for st in streams:
-            if st is not None:
-                st.wait_stream(main)
-        acts = [(torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)) for _ in range(G)]
-        lib = env._b.lib
+        col = _Collection(asynchronous, duration, wall.clone())
         # the loop without waits (see __init__, record_on_device)
-        fast = (self.record_on_device and not asynchronous and G == 1 and self.act_fn is None and self.policy is not None and B > 0
+        fast = (self.record_on_device and not asynchronous and self.act_fn is None and self.policy is not None and B > 0
                 and self.policy._use_kernels() and env.graph_kernel_fits)
-        LAG, R = 4, 8  # flags are read at most LAG steps late; rings of R slots for what a step leaves for the host
-        arena = None
-        if fast:
-            cuda = dev.type == "cuda"
-            pin = (lambda t: t.pin_memory()) if cuda else (lambda t: t)
-            cap0 = None
-            if self._arena_sizes:
-                d = env.dims
-                step_max = (B * d.node_cap, B * d.edge_cap, B * d.job_cap, B)
-                cap0 = [int(1.1 * c) + (LAG + 4) * m for c, m in zip(self._arena_sizes, step_max)]
-            arena = GraphArena(env, cap0)
-            ring_flags, ring_cur = pin(torch.zeros((R, 8), dtype=torch.int32)), pin(torch.zeros((R, 8), dtype=torch.int64))
-            ring_acts = [(torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)) for _ in range(R)]
-            ring_ev = [torch.cuda.Event() for _ in range(R)] if cuda else None
-        n_kept, kept_sizes = 0, [0, 0, 0, 0]  # fast: steps whose observations are part of the record, the arena's cursors after them
-        n_lockstep = 0  # steps a loop that reads every step's flags before issuing the next would have issued (a dropped last step included)
-        calls0 = getattr(self.policy, "_calls", 0) if fast else 0
-        graphs: dict[tuple[int, int], dict[str, Any]] = {}
-        issued = [0] * G             # steps enqueued per group
-        unread: list[Any] = [None] * G  # (t, graph, stage_idx, num_exec) of the group's step whose flags have not been read yet
-        alive = [B > 0] * G
-        n_failed = 0
-
-        def sync_all():
-            if use_streams:
-                for st in streams:
-                    st.synchronize()
-
-        def read_flags(k: int) -> None:
-            """what became of group k's last step: the ONE device->host read per group and step beside the graph totals"""
-            t, g, stage_idx, num_exec = unread[k]
-            unread[k] = None
-            handle_flags(k, t, g, stage_idx, num_exec, flags[t, k, :5].tolist())
-
-        def handle_flags(k: int, t: int, g, stage_idx, num_exec, vals) -> None:
-            nonlocal n_failed, n_kept, kept_sizes, n_lockstep
-            any_bad, any_done, any_left, bad_env, any_recorded = vals
-            n_lockstep = t + 1
-            if any_bad:
-                n_bad = int(pending.sum()) - n_failed
-                n_failed += n_bad
-                self.env_errors += n_bad
-                if self.on_env_error == "raise":
-                    from .binding import ERROR_NAMES
-                    b = bad_env - 1
-                    code = int(env.obs_i32[b, 7])
-                    err = RuntimeError(f"env {b} (seed {int(self.seeds[b] - self.seed_step)}), rollout step {t}: "
-                                       f"{ERROR_NAMES.get(code, code)}; action stage_idx={int(stage_idx[b])} num_exec={int(num_exec[b])}")
-                    # what a bug report needs: the env's seed, time limit and action history
-                    err.case = {"seed": int(self.seeds[b] - self.seed_step), "time_limit": float(self.tl_env.time_limit[b]), "code": code,
-                                "stage_idx": [int(x) for x in rec["stage_sel"][:t, b]] + [int(stage_idx[b])],
-                                "num_exec": [int(x) + 1 for x in rec["exec_sel"][:t, b]] + [int(num_exec[b])]}
-                    raise err
-                # truncate: the failing step is not recorded and the env sits out the rest of this
-                # collection (async: it starts its next episode at the next collection)
-                if not any_recorded:
-                    alive[k] = False
-                    return
-            if g is not None:
-                graphs[(t, k)] = g
-            n_kept = t + 1
-            if arena is not None:
-                kept_sizes = list(arena.seen)  # (take_late has just noted the cursors after this step)
-            if asynchronous and any_done:
-                done = rec["resets"][t].view(torch.bool)
-                self._reset(mask=done if member_b[k] is None else done & member_b[k])
-            alive[k] = bool(any_left)
-
-        def enqueue(k: int) -> None:
-            nonlocal cap, flags
-            t = issued[k]
-            if t == cap:  # grow the record (every stream has to be done with the old arrays)
-                sync_all()
-                for name in rec:
-                    rec[name] = torch.cat([rec[name], torch.zeros_like(rec[name])])
-                flags = torch.cat([flags, torch.zeros_like(flags)])
-                cap *= 2
-            act_b = active.view(torch.bool) if member_b[k] is None else active.view(torch.bool) & member_b[k]
-            if fast:
-                arena.ensure(drain_all)
-                g = self.env.decima_graph_on_device(act_b)  # (sizes stay on the device; appended to the arena below)
-            else:
-                g = self.env.decima_graph(act_b)  # recorded for training
-            a = self.act_fn(g, self.step_counts) if self.act_fn is not None else self.policy.act(g, self.generator)
-            if fast:
-                hint = g["totals_hint"].tolist()
-                arena.append(g, rows_hint=max(5 * hint[0], hint[1], hint[2], B) if hint[0] >= 0 else 0)
-            sel = [a[n] if a[n].dtype == torch.int64 and a[n].is_contiguous() else a[n].to(torch.int64).contiguous() for n in ("stage_sel", "job_idx", "exec_sel")]
-            lg = a["lgprob"] if a["lgprob"].dtype == torch.float32 and a["lgprob"].is_contiguous() else a["lgprob"].float().contiguous()
-            stage_idx, num_exec = ring_acts[t % R] if fast else acts[k]
-            c = SssCollectArgs(B, int(asynchronous), t, float(duration), env.obs_f64.data_ptr(), env.obs_i32.data_ptr(), env.obs_i32.stride(0),
-                               self.tl_env.time_limit.data_ptr(), active.data_ptr(), wall.data_ptr(), elapsed.data_ptr(), self.step_counts.data_ptr(),
-                               pending.data_ptr(), sel[0].data_ptr(), sel[1].data_ptr(), sel[2].data_ptr(), lg.data_ptr(), stage_idx.data_ptr(), num_exec.data_ptr(),
-                               *(rec[name].data_ptr() for name, _ in spec), flags[t, k].data_ptr(), member[k].data_ptr() if member[k] is not None else None)
-            stream = env._stream()
-            with device_of(dev):
-                env._b.check(lib.sss_collect_step(ctypes.byref(c), 0, stream))
-            env.step_async(stage_idx, num_exec)
-            with device_of(dev):
-                env._b.check(lib.sss_collect_step(ctypes.byref(c), 1, stream))
-            if fast:  # what the host wants of this step, without waiting for it: its flags and the arena's cursors after it
-                ring_flags[t % R].copy_(flags[t, k], non_blocking=True)
-                ring_cur[t % R].copy_(arena.cursor, non_blocking=True)  # (ring_cur[.., 4] = steps appended: which step the cursors are of)
-                if ring_ev is not None:
-                    ring_ev[t % R].record(torch.cuda.current_stream(dev))
-                unread[k] = None
-                late.append((t, stage_idx, num_exec))
-            else:
-                unread[k] = (t, g, stage_idx, num_exec)
-            issued[k] = t + 1
-
-        late: list[Any] = []  # fast: steps enqueued whose flags have not been looked at, oldest first
-
-        def take_late() -> None:
-            """the oldest enqueued step's flags (waits for that step if it has not finished)"""
-            t, stage_idx, num_exec = late.pop(0)
-            if ring_ev is not None:
-                ring_ev[t % R].synchronize()
-            arena.note(ring_cur[t % R].tolist(), t + 1)
-            handle_flags(0, t, None, stage_idx, num_exec, ring_flags[t % R, :5].tolist())
-
-        def drain_all() -> None:
-            while late and alive[0]:
-                take_late()
-
-        try:
-            while fast and alive[0]:
-                # look at the steps that have finished, and never run more than LAG steps ahead of the flags
-                while late and alive[0] and (len(late) >= LAG or ring_ev is None or ring_ev[late[0][0] % R].query()):
-                    take_late()
-                if alive[0]:
-                    enqueue(0)
-                    if ring_ev is None:
-                        take_late()
-            while not fast and (any(alive) or any(u is not None for u in unread)):
-                for k in range(G):
-                    with (torch.cuda.stream(streams[k]) if streams[k] is not None else contextlib.nullcontext()):
-                        if unread[k] is not None:
-                            read_flags(k)
-                        if alive[k]:
-                            enqueue(k)
-        finally:
-            sync_all()
-            if use_streams:
-                for st in streams:
-                    main.wait_stream(st)
-        if n_failed:
-            self._pending_reset = pending.view(torch.bool)
-        self._obs, self._wall = True, wall  # (_obs: the envs are inside their episodes)
-        keys = sorted(graphs)
-        T = n_kept if fast else max((t for t, _ in keys), default=-1) + 1
-        out = {name: rec[name][:T] for name, _ in spec}
-        obs_index = None
-        if G > 1:  # observation (t, b) sits in the graph its group recorded at step t
-            pos = np.full((max(T, 1), G), 0, dtype=np.int64)
-            for i, (t, k) in enumerate(keys):
-                pos[t, k] = i
-            obs_index = torch.from_numpy(pos[:T]).to(dev)[:, group_of] * B + torch.arange(B, device=dev)[None, :]
-        if fast:
-            if dev.type == "cuda":
-                torch.cuda.current_stream(dev).synchronize()
-            graph = arena.finish(T, kept_sizes)  # (a last step that failed for every env left is dropped, like the steps enqueued behind the end)
-            # the steps enqueued behind the last one found every env frozen, but each took a draw counter of the policy's sampling
-            # stream (decima._sample_kernels): hand them back, so that the next collection draws what it would have drawn - the loop
-            # that waits for every step's flags has issued n_lockstep steps (a last step that failed for every env left took its
-            # counter too, although it is not part of the record)
-            if hasattr(self.policy, "_calls"):
-                self.policy._calls = calls0 + n_lockstep
-            self._arena_sizes = [int(graph["x"].shape[0]), int(graph["src"].numel()), int(graph["job_obs"].numel()), T * B]
-        else:
-            graph = concat_graphs([graphs[key] for key in keys])
-        return Rollouts(graph=graph, active=out["active"].view(torch.bool), t_before=out["t_before"], t_after=out["t_after"],
-                        rewards=out["rewards"], stage_sel=out["stage_sel"], job_idx=out["job_idx"], exec_sel=out["exec_sel"],
-                        lgprobs=out["lgprobs"], resets=out["resets"].view(torch.bool), stats=self._stats() if with_stats else {}, obs_index=obs_index)
+        graph = self._collect_ahead(col) if fast else self._collect_waiting(col)
+        if col.n_failed:
+            self._pending_reset = col.pending.view(torch.bool)
+        self._wall = col.wall
+        return Rollouts(graph=graph, stats=self._stats() if with_stats else {}, **col.fields())
 
     def collect_sync(self, with_stats: bool = True) -> Rollouts:
         """one full episode per env (rollout_worker.py:133-159)"""
@@ -494,9 +462,7 @@ def discounted_returns(ro: Rollouts, beta: float, binding=None) -> torch.Tensor:
     T, B = ro.active.shape
     b = _record_kernels(ro, binding)
     if b is not None and T > 0 and B > 0:  # one kernel, a thread per env (the loop below: T x 5 launches, 0.30 s at BASELINE config 5)
-        import ctypes
-
-        from .binding import SssReturnsArgs, device_of
+        from .binding import SssReturnsArgs
         dev = ro.active.device
         act, tb, ta, rw = ro.active.contiguous().view(torch.uint8), _c64(ro.t_before), _c64(ro.t_after), _c64(ro.rewards)
         out = torch.empty((T, B), dtype=torch.float64, device=dev)
@@ -586,9 +552,7 @@ class DeviceDifferentialReturns:
         return np.zeros((self.cap, 2)) if self._win is None else self._win[self._cur].cpu().numpy()
 
     def __call__(self, ro: Rollouts) -> torch.Tensor:
-        import ctypes
-
-        from .binding import SssDiffretArgs, SssRewardWindowArgs, device_of, reward_window_scratch
+        from .binding import SssDiffretArgs, SssRewardWindowArgs, reward_window_scratch
         b = _record_kernels(ro, self.binding)
         if b is None:
             raise RuntimeError("DeviceDifferentialReturns: the record is not on a GPU and no binding was given (DifferentialReturns is the host form)")
@@ -670,9 +634,7 @@ def sequence_baselines(ro: Rollouts, values: torch.Tensor, num_sequences: int, n
     G, R = num_sequences, num_rollouts
     b = _record_kernels(ro, binding)
     if b is not None and T > 0 and B > 0:  # one kernel, a thread per (step, env) query (below: ~20 operations on [G, R, R, T] tensors)
-        import ctypes
-
-        from .binding import SssBaselineArgs, device_of
+        from .binding import SssBaselineArgs
         dev = ro.active.device
         act, ts, ys = ro.active.contiguous().view(torch.uint8), _c64(ro.t_before), _c64(values)
         n = ro.active.sum(0).to(torch.int64).contiguous()
@@ -900,8 +862,9 @@ class Trainer:
         self.deterministic = bool(train_cfg.get("deterministic", False) if deterministic is None else deterministic)
         if self.deterministic and self.rollout_duration:
             raise ValueError("trainer: `deterministic: true` cannot be combined with `rollout_duration` (asynchronous collection is paced by the wall clock)")
-        if self.deterministic and int(train_cfg.get("collector_groups", 1)) > 1:
-            raise ValueError("trainer: `deterministic: true` needs `collector_groups: 1` (several groups of envs on their own streams are not verified to be reproducible)")
+        if int(train_cfg.get("collector_groups", 1)) != 1:
+            raise ValueError("trainer: `collector_groups` other than 1 is no longer supported (alternating groups of envs on their own streams were measured "
+                             "slower on one MI355X, profiles/r03_ppo.md, never verified with `deterministic: true`, and removed): drop the key")
         self.checkpointing_freq = int(train_cfg.get("checkpointing_freq", 50))
         self.artifacts_dir = train_cfg.get("artifacts_dir", "artifacts")
         self.env_cfg = dict(env_cfg)
@@ -933,10 +896,7 @@ class Trainer:
         gen = torch.Generator(device=dev if dev.type == "cuda" else "cpu")
         gen.manual_seed(self.seed * 1000003 + self.rank)
         self.collector = RolloutCollector(self.env, self.env_cfg["mean_time_limit"], base_seeds, total_sequences, E,
-                                          policy=self.policy, generator=gen, on_env_error=train_cfg.get("on_env_error", "raise"),
-                                          # (`collector_groups` > 1: alternating groups of envs on their own streams - measured
-                                          # slower on one MI355X, profiles/r03_ppo.md; one group is the default)
-                                          groups=int(train_cfg.get("collector_groups", 1)))
+                                          policy=self.policy, generator=gen, on_env_error=train_cfg.get("on_env_error", "raise"))
         self.ppo = PPO(self.policy, train_cfg, generator=gen)
         self.history: list[dict[str, float]] = []
 

@@ -155,6 +155,24 @@ def test_no_cpu_fallback():
         load_library("/nonexistent/libsss_hip.so")
 
 
+def test_a_library_from_other_sources_is_stale_whatever_its_age(tmp_path):
+    """build.needs_build goes by the digest of sources and flags kept next to the library, not by modification times: a library
+    copied in from another checkout (newer than every source, another ABI) is rebuilt, and so is one built with other flags"""
+    from spark_sched_sim_amd import build
+
+    out = tmp_path / "libsss_hip_x.so"
+    assert build.needs_build(str(out))
+    out.write_bytes(b"newer than every source")
+    assert build.needs_build(str(out))  # no stamp: nobody knows what it was built from
+    stamp = tmp_path / "libsss_hip_x.so.stamp"
+    stamp.write_text(build.source_digest(("-DOTHER",)) + "\n")
+    assert build.needs_build(str(out)) and not build.needs_build(str(out), ("-DOTHER",))
+    stamp.write_text(build.source_digest() + "\n")
+    assert not build.needs_build(str(out))
+    out.unlink()
+    assert build.needs_build(str(out))
+
+
 def test_header_offsets_match_layout(tmp_path):
     """vec_env.HDR_OFF mirrors struct SssHdr (csrc/sss_layout.h)"""
     from spark_sched_sim_amd.vec_env import HDR_OFF, HDR_PROF

@@ -402,32 +402,20 @@ def test_record_kernels_on_the_host_backend():
     check_record_kernels(Binding(load_emu()), "cpu")
 
 
-def test_two_groups_of_envs_record_what_one_group_records():
-    """`RolloutCollector(groups=2)` - the envs take their steps in two alternating groups (on two streams on the GPU), the
-    flags of a group's step are read one step late - against `groups=1`: the same record per env, and every sample's
-    observation id (`Rollouts.sample_ids`) points at the same observation of the recorded graph"""
-    import torch
+def test_trainer_refuses_the_removed_collector_groups_key(tmp_path):
+    """`collector_groups` (alternating groups of envs on their own streams) was removed: a config that still asks for several
+    groups is refused by name, not silently run with one; `collector_groups: 1` says what the collector does and is accepted"""
+    import pytest
 
     from emu_util import load_emu
-    from spark_sched_sim_amd import VecSparkSchedSimEnv
-    from spark_sched_sim_amd.training import RolloutCollector
-    from training_util import counter_act_fn
+    from spark_sched_sim_amd.training import make_trainer
+    from training_util import reference_smoke_test_config
 
-    cfg = dict(num_executors=10, job_arrival_cap=8, job_arrival_rate=4.0e-5, moving_delay=2000.0, warmup_delay=1000.0)
-    res = {}
-    for groups in (1, 2):
-        for mode in ("sync", "async"):
-            env = VecSparkSchedSimEnv(cfg, 5, device="cpu", auto_reset=False, _lib=load_emu())
-            col = RolloutCollector(env, 5.0e5, [11, 12, 13, 14, 15], seed_step=5, num_executors=10, act_fn=counter_act_fn, groups=groups)
-            ro = col.collect_sync(with_stats=False) if mode == "sync" else col.collect_async(2.0e5, with_stats=False)
-            ids = ro.sample_ids()
-            res[(groups, mode)] = ([ro.rollout(b) for b in range(5)], ro.graph["obs_nodes"][ids], ro.graph["obs_jobs"][ids], ro.flat(ro.rewards))
-            env.close()
-    for mode in ("sync", "async"):
-        one, two = res[(1, mode)], res[(2, mode)]
-        for ra, rb in zip(one[0], two[0]):
-            assert ra.keys() == rb.keys() and all((ra[k] == rb[k]).all() and ra[k].shape == rb[k].shape for k in ra)
-        assert one[1].numel() > 50 and all(torch.equal(a, b) for a, b in zip(one[1:], two[1:]))
+    cfg = reference_smoke_test_config(str(tmp_path))
+    with pytest.raises(ValueError, match="collector_groups"):
+        make_trainer({**cfg, "trainer": {**cfg["trainer"], "collector_groups": 2}}, device="cpu", _lib=load_emu())
+    tr = make_trainer({**cfg, "trainer": {**cfg["trainer"], "collector_groups": 1}}, device="cpu", _lib=load_emu())
+    tr.env.close()
 
 
 def test_sum_order_of_the_baseline_mean_is_numpys():

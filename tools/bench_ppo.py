@@ -30,7 +30,6 @@ def main():
     ap.add_argument("--rollout-duration", type=float, default=0.0)
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--device-index", type=int, default=None)
-    ap.add_argument("--collector-groups", type=int, default=1)
     ap.add_argument("--deterministic", action="store_true", help="the trainer's deterministic mode (`trainer: deterministic: true`): the iterations run "
                     "under training.deterministic_scope, the update's row sums in a fixed order")
     ap.add_argument("--differential", type=int, nargs="?", const=200_000, default=None, metavar="CAP",
@@ -55,8 +54,7 @@ def main():
         raise SystemExit(launch_ranks(a.gpus, [osp.abspath(__file__)] + sys.argv[1:]))
     train = dict(trainer_cls="PPO", num_iterations=1, num_sequences=a.sequences, num_rollouts=a.rollouts, seed=42,
                  checkpointing_freq=10 ** 9, num_epochs=3, num_batches=10, clip_range=0.2, target_kl=0.01, entropy_coeff=0.04,
-                 beta_discount=5.0e-3, opt_cls="Adam", opt_kwargs=dict(lr=3.0e-4), max_grad_norm=0.5, artifacts_dir="/tmp/sss_ppo",
-                 collector_groups=a.collector_groups, deterministic=a.deterministic)
+                 beta_discount=5.0e-3, opt_cls="Adam", opt_kwargs=dict(lr=3.0e-4), max_grad_norm=0.5, artifacts_dir="/tmp/sss_ppo", deterministic=a.deterministic)
     if a.rollout_duration:
         train["rollout_duration"] = a.rollout_duration
     if a.differential is not None:
