@@ -348,6 +348,11 @@ typedef struct sss_decima_policy_args {
   uint64_t* prof_dev;      /* nullable: u64[num_envs][8] shader cycles per phase + depth + node count */
 } sss_decima_policy_args;
 int sss_decima_policy(sss_handle* h, const sss_decima_policy_args* a, void* stream);
+/* The same kernel with both decisions taken as the arg-max of its own scores instead of drawn (a second instantiation of the
+ * device function; rng_seed / rng_counter are ignored): the stage with the largest score among the schedulable ones, then the
+ * executor count with the largest score among the allowed ones - ties go to the lowest index, a NaN never wins. lgprob is the
+ * log-softmax of the chosen entries, computed as the draw computes it. */
+int sss_decima_policy_argmax(sss_handle* h, const sss_decima_policy_args* a, void* stream);
 
 /* The two softmax draws of DecimaScheduler.schedule (schedulers/decima/scheduler.py:80-99) for the
  * sss_gnn_launch pipeline, one wavefront per observation, same Gumbel-max stream as sss_decima_policy.
@@ -376,6 +381,16 @@ typedef struct sss_decima_sample_args {
   uint8_t* any_stage_dev;
 } sss_decima_sample_args;
 int sss_decima_sample(int n_obs, int which, const sss_decima_sample_args* a, void* stream);
+/* The arg-max counterpart of the two draws (second instantiations of the same device functions; rng_seed / rng_counter are
+ * ignored), same inputs, same outputs.
+ * which = 0: the candidates are the slots i < obs_nodes[env] with sched_rank[i] >= 0 and a score other than -inf - the draw's own
+ * filter: a stale finite score in a slot that is no schedulable stage loses. The largest score wins; TIES GO TO THE LOWEST i
+ * (-0.0 and +0.0 tie); a NaN never wins. Writes any_stage, job_gid, stage_idx, stage_sel, job_idx as the draw does and
+ * lgprob = s_sel - M - logf(S) from the draw's online log-sum-exp: for the same selection, the draw's bits. Nothing schedulable:
+ * stage_idx = -1, zeros elsewhere, lgprob = 0.
+ * which = 1: the candidates are the counts c < E with a score other than -inf (lanes stride over c, any E); the largest score wins,
+ * ties go to the lowest c; lgprob += its log-softmax. No candidate, or any_stage == 0: exec_sel = 0, num_exec = 1, lgprob unchanged. */
+int sss_decima_argmax(int n_obs, int which, const sss_decima_sample_args* a, void* stream);
 
 /* Decima's encoder for one batch of observations in ONE call (scheduler.py:142-283: node embeddings by message passing over
  * the DAG layers, per-job and per-observation summaries): the launches sss_gnn_launch offers one by one - PREP, SINK, one LAYER
@@ -777,6 +792,28 @@ struct sss_timeline_render_args {
   uint8_t* rgb_dev;
 };
 int sss_timeline_render(sss_handle* h, const struct sss_timeline_render_args* a, void* stream);
+
+/* The episode metrics of every env in one launch, one wavefront per env, from the env's block of the state arena (t_arrival,
+ * t_completed, the duration ring, and wall_time, next_arrival, n_completed, n_active, dur_n, dur_head of its header). Nothing is
+ * written to the arena. The definitions are those of the reference's host functions (spark_sched_sim/metrics.py:4-23,
+ * spark_sched_sim.py:243-245), every sum in the ORDER the host takes - the order is the definition, the results carry the host's bits:
+ *   n = next_arrival; d_j = min(t_completed[j], wall_time) - t_arrival[j] for j < n, in job-id order
+ *   stats[0] = n
+ *   stats[1] = ((0.0 + d_0) + d_1) + ...                                        (Python's sum)
+ *   stats[2] = numpy.mean(d): numpy's pairwise summation order, then one division by n; NaN for n = 0
+ *   stats[3] = stats[1] / wall_time                                             (IEEE division: NaN at wall_time == 0 with no jobs)
+ *   stats[4] = numpy.mean(the ring's dur_n entries from dur_head on, i.e. in deque order) * 1e-3; NaN for an empty ring
+ *   stats[5], [6], [7] = n_completed, n_active, wall_time
+ *   pct[k] = numpy.percentile(d, q[k]), default method: d sorted ascending, quant = q / 100,
+ *            vi = (n - 1) * quant (numpy's own index of its "linear" method), lo = floor(vi), hi = lo + 1, both n - 1 where
+ *            vi >= n - 1 and 0 where vi < 0, g = vi - lo, result a + (b - a) * g, replaced by b - (b - a) * (1 - g) where g >= 0.5
+ *            (a, b = the sorted values at lo, hi); NaN for n = 0
+ * q_dev f64[n_q], n_q in 0..16, every value in [0, 100] (the caller's duty - the values live on the device; the kernel gives NaN
+ * for any other). stats_dev f64[num_envs][8], pct_dev f64[num_envs][n_q]; sorted_dev (nullable) f64[num_envs][job_cap] receives
+ * the sorted durations, the rest of a row NaN; active_dev (nullable) u8[num_envs]: the rows of envs with 0 are left untouched.
+ * job_cap <= 1024. (Plain parameters, like sss_prefix_rows: there is no argument structure to keep in step with the binding.) */
+int sss_job_stats(sss_handle* h, int n_q, const double* q_dev, double* stats_dev, double* pct_dev, double* sorted_dev, const uint8_t* active_dev,
+                  void* stream);
 
 const char* sss_last_error(void);
 void sss_destroy(sss_handle* h);

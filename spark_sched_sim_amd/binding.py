@@ -170,6 +170,10 @@ class SssTimelineRenderArgs(C.Structure):  # include/sss.h sss_timeline_render_a
     _fields_ = [("env_ids_dev", C.c_void_p), ("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("pad_", C.c_int32), ("rgb_dev", C.c_void_p)]
 
 
+JOB_STATS_COLUMNS = ("num_jobs", "total_job_time", "avg_job_duration", "avg_num_jobs", "avg_completed_job_duration", "num_completed_jobs", "num_active_jobs",
+                     "wall_time")  # include/sss.h sss_job_stats: stats[0..7]
+JOB_STATS_MAX_Q = 16
+
 REWARD_WINDOW_CHUNK = 64  # include/sss.h SSS_REWARD_WINDOW_CHUNK
 
 
@@ -189,7 +193,7 @@ class SssArenaArgs(C.Structure):  # include/sss.h sss_arena_args
 
 EXPORTS = ["sss_query_dims", "sss_create", "sss_bind_buffers", "sss_reset", "sss_step", "sss_step_bounded", "sss_policy", "sss_rollout",
            "sss_decima_graph_build", "sss_decima_layer_lists", "sss_prefix_rows", "sss_decima_policy", "sss_decima_sample", "sss_gnn_launch",
-           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_bind_timeline", "sss_timeline_render", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
+           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_bind_timeline", "sss_timeline_render", "sss_decima_argmax", "sss_decima_policy_argmax", "sss_job_stats", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
 POLICY_IDS = {"fair": 0, "fifo": 1, "hash": 2, "wfair": 3, "sjfcp": 4}
 WFAIR_ALPHA_RANGE = (-4, 4)  # sss_policy / sss_rollout: the weighted-fair exponent (param of policy 3)
 # the argument structures of include/sss.h and their mirrors here (Binding.check_abi)
@@ -253,6 +257,9 @@ class Binding:
         L.sss_differential_returns.argtypes = [C.POINTER(SssDiffretArgs), C.c_void_p]
         L.sss_bind_timeline.argtypes = [C.c_void_p, C.POINTER(SssTimeline)]
         L.sss_timeline_render.argtypes = [C.c_void_p, C.POINTER(SssTimelineRenderArgs), C.c_void_p]
+        L.sss_decima_argmax.argtypes = [C.c_int, C.c_int, C.POINTER(SssDecimaSampleArgs), C.c_void_p]
+        L.sss_decima_policy_argmax.argtypes = [C.c_void_p, C.POINTER(SssDecimaPolicyArgs), C.c_void_p]
+        L.sss_job_stats.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
         L.sss_bit_lists.argtypes = [C.POINTER(SssBitListArgs), C.c_void_p]
         L.sss_arena_append.argtypes = [C.POINTER(SssArenaArgs), C.c_void_p]
         L.sss_rows_op.argtypes = [C.POINTER(SssRowsArgs), C.c_void_p]

@@ -65,7 +65,19 @@ SSS_DEV float dp_gumbel(uint64_t seed, uint64_t counter, int env, uint32_t idx, 
   float u = fminf(((float)(uint32_t)(z >> 40) + 0.5f) * (1.0f / 16777216.0f), 0.99999994f);
   return -logf(-logf(u));
 }
+// what a candidate competes with: its Gumbel-perturbed score (a draw), or the score itself (arg-max; + 0.0f turns -0.0 into +0.0,
+// so that the two zeros tie as they compare)
+template <bool ARGMAX>
+SSS_DEV float dp_key(float sc, uint64_t seed, uint64_t counter, int env, uint32_t idx, uint32_t draw) {
+  if (ARGMAX) return sc + 0.0f;
+  return sc + dp_gumbel(seed, counter, env, idx, draw);
+}
 
+// ARGMAX: the second instantiation (sss_decima_policy_argmax): both decisions are the arg-max of the scores instead of draws - the key
+// of a candidate is its score (-0.0 counted as +0.0) instead of score + Gumbel, so the strict `>` of a lane's scan keeps the
+// lane's FIRST maximum, dp_wave_argmax gives equal keys of different lanes to the smallest index, and a NaN (no `>` holds) never
+// wins. Everything else - the filter, the online log-sum-exp, the outputs - is the draw's, instruction for instruction.
+template <bool ARGMAX = false>
 SSS_DEV void decima_policy_wave(const SssLayout& L, const SssBuffers& B, int E, const SssDecimaPolicyArgs& d, int env, uint8_t* lds) {
   constexpr int F = GNN_EMB;
   int lane = wave_lane() & 63;  // several envs (wavefronts) may share a workgroup
@@ -277,7 +289,7 @@ SSS_DEV void decima_policy_wave(const SssLayout& L, const SssBuffers& B, int E, 
       GNN_UNROLL for (int q = 0; q < F; q++) x[GNN_NF + 2 * F + q] = hglob[q];
       gnn_hidden<GNN_NF + 3 * F, 64, 64, 1>(d.w_stage, x, h2, 0.0f);
       gnn_out<GNN_NF + 3 * F, 64, 64, 1>(d.w_stage, h2, 1.0f, [&](int, float v) { sc = v; });
-      float key = sc + dp_gumbel(d.rng_seed, d.rng_counter, env, (uint32_t)i, 0);
+      float key = dp_key<ARGMAX>(sc, d.rng_seed, d.rng_counter, env, (uint32_t)i, 0);
       if (key > best_key) best_key = key, best_i = (uint32_t)i, best_score = sc;
       float m_new = sc > m_run ? sc : m_run;
       s_run = s_run * expf(m_run - m_new) + expf(sc - m_new);
@@ -333,7 +345,7 @@ SSS_DEV void decima_policy_wave(const SssLayout& L, const SssBuffers& B, int E, 
     if (c < cap) esc[q] = v0;
     if (d.exec_scores) d.exec_scores[(size_t)env * E + c] = esc[q];
     if (esc[q] != -__builtin_inff()) {
-      float key = esc[q] + dp_gumbel(d.rng_seed, d.rng_counter, env, (uint32_t)c, 1);
+      float key = dp_key<ARGMAX>(esc[q], d.rng_seed, d.rng_counter, env, (uint32_t)c, 1);
       if (key > ekey) ekey = key, ebest = esc[q], ebest_c = (uint32_t)c;
       if (esc[q] > emax) emax = esc[q];
     }
@@ -387,7 +399,8 @@ struct SssDecimaSampleArgs {
   uint8_t* any_stage;
 };
 
-SSS_KERNEL void sss_decima_sample_stage_kernel(SssDecimaSampleArgs d) {
+template <bool ARGMAX>
+SSS_DEV void decima_sample_stage_wave(const SssDecimaSampleArgs& d) {
   int env = wave_env(), lane = wave_lane();
   int n = (int)d.obs_nodes[env];
   const float* row = d.stage_scores + (size_t)env * d.n_pad;
@@ -399,7 +412,7 @@ SSS_KERNEL void sss_decima_sample_stage_kernel(SssDecimaSampleArgs d) {
     // (a slot that is not a schedulable stage holds -inf - or, in a score matrix that is refilled without being cleared, whatever an
     // earlier pass left there: the stage's rank decides as well)
     if (rank[i] < 0 || sc == -__builtin_inff()) continue;
-    float key = sc + dp_gumbel(d.rng_seed, d.rng_counter, env, (uint32_t)i, 0);
+    float key = dp_key<ARGMAX>(sc, d.rng_seed, d.rng_counter, env, (uint32_t)i, 0);
     if (key > best_key) best_key = key, best_i = (uint32_t)i, best_score = sc;
     float m_new = sc > m_run ? sc : m_run;
     s_run = s_run * expf(m_run - m_new) + expf(sc - m_new);
@@ -427,7 +440,10 @@ SSS_KERNEL void sss_decima_sample_stage_kernel(SssDecimaSampleArgs d) {
   }
 }
 
-SSS_KERNEL void sss_decima_sample_exec_kernel(SssDecimaSampleArgs d) {
+SSS_KERNEL void sss_decima_sample_stage_kernel(SssDecimaSampleArgs d) { decima_sample_stage_wave<false>(d); }
+
+template <bool ARGMAX>
+SSS_DEV void decima_sample_exec_wave(const SssDecimaSampleArgs& d) {
   int env = wave_env(), lane = wave_lane();
   bool live = d.any_stage[env] != 0;
   const float* row = d.exec_scores + (size_t)env * d.E;
@@ -437,7 +453,7 @@ SSS_KERNEL void sss_decima_sample_exec_kernel(SssDecimaSampleArgs d) {
   for (int c = lane; live && c < d.E; c += 64) {
     float esc = row[c];
     if (esc == -__builtin_inff()) continue;
-    float key = esc + dp_gumbel(d.rng_seed, d.rng_counter, env, (uint32_t)c, 1);
+    float key = dp_key<ARGMAX>(esc, d.rng_seed, d.rng_counter, env, (uint32_t)c, 1);
     if (key > ekey) ekey = key, ebest = esc, ebest_c = (uint32_t)c;
     if (esc > emax) emax = esc;
   }
@@ -460,3 +476,32 @@ SSS_KERNEL void sss_decima_sample_exec_kernel(SssDecimaSampleArgs d) {
     if (any_exec) d.lgprob[env] += esel - EM - logf(ES);
   }
 }
+SSS_KERNEL void sss_decima_sample_exec_kernel(SssDecimaSampleArgs d) { decima_sample_exec_wave<false>(d); }
+
+// ---- the arg-max counterparts (include/sss.h sss_decima_argmax, sss_decima_policy_argmax) and their launches ---------------------
+// The same device functions instantiated with ARGMAX = true. The launches live here in both forms: kernels for the HIP library
+// (the one-launch policy's, which stages the parameters in LDS first, is next to its sampling twin in sss_hip.hip), plain
+// emulator launches of the same functions for builds without a device compiler.
+#if defined(__HIPCC__)
+SSS_KERNEL void sss_decima_argmax_stage_kernel(SssDecimaSampleArgs d) { decima_sample_stage_wave<true>(d); }
+SSS_KERNEL void sss_decima_argmax_exec_kernel(SssDecimaSampleArgs d) { decima_sample_exec_wave<true>(d); }
+static int be_launch_decima_argmax(int n_obs, int which, const SssDecimaSampleArgs& d, void* stream) {
+  if (which == 0) hipLaunchKernelGGL(sss_decima_argmax_stage_kernel, dim3(n_obs), dim3(64), 0, (hipStream_t)stream, d);
+  else hipLaunchKernelGGL(sss_decima_argmax_exec_kernel, dim3(n_obs), dim3(64), 0, (hipStream_t)stream, d);
+  return (int)hipGetLastError();
+}
+#else
+#include <functional>
+namespace emu {
+void launch(int grid, const std::function<void()>& body);
+}
+static int be_launch_decima_argmax(int n_obs, int which, const SssDecimaSampleArgs& d, void*) {
+  if (which == 0) emu::launch(n_obs, [&]() { decima_sample_stage_wave<true>(d); });
+  else emu::launch(n_obs, [&]() { decima_sample_exec_wave<true>(d); });
+  return 0;
+}
+static int be_launch_decima_policy_argmax(const SssLayout& L, const SssBuffers& B, int E, const SssDecimaPolicyArgs& d, void*) {
+  emu::launch(L.num_envs, [&]() { decima_policy_wave<true>(L, B, E, d, wave_env(), g_dp_lds); });
+  return 0;
+}
+#endif

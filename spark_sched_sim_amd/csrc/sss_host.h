@@ -18,6 +18,7 @@
 #include "sss_narrow.h"
 #include "sss_wide.h"
 #include "sss_timeline.h"  // the Gantt rasteriser and its launch (a kernel, or - without a device compiler - plain loops)
+#include "sss_jobstats.h"  // the per-env job statistics and their launch, in the same two forms
 
 // envs with more than 64 executors run on the wide instantiation of the kernels (sss_wide.h)
 static bool sss_is_wide(int num_executors) { return num_executors > 64; }
@@ -484,6 +485,23 @@ extern "C" int sss_timeline_render(sss_handle* h, const struct sss_timeline_rend
   return 0;
 }
 
+extern "C" int sss_job_stats(sss_handle* h, int n_q, const double* q_dev, double* stats_dev, double* pct_dev, double* sorted_dev, const uint8_t* active_dev,
+                             void* stream) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (n_q < 0 || n_q > SSS_JS_MAX_Q) return sss_fail(-42, "sss_job_stats: n_q must be in 0..16, got " + std::to_string(n_q));
+  if (!stats_dev) return sss_fail(-42, "sss_job_stats: stats_dev is NULL");
+  if (n_q > 0 && (!q_dev || !pct_dev)) return sss_fail(-42, "sss_job_stats: q_dev / pct_dev is NULL with n_q > 0");
+  if (h->L.J_cap > SSS_MAX_JOBS) return sss_fail(-42, "sss_job_stats: job capacity beyond the kernel's LDS working set");
+  SssJobStatsArgs r;
+  r.state = (const uint8_t*)h->B.state, r.env_stride = h->L.env_stride, r.off_t_arrival = h->L.off_t_arrival;
+  r.off_t_completed = h->L.off_t_completed, r.off_dur_ring = h->L.off_dur_ring, r.num_envs = h->L.num_envs, r.J_cap = h->L.J_cap;
+  r.n_q = n_q, r.pad_ = 0, r.q = q_dev, r.stats = stats_dev, r.pct = pct_dev, r.sorted = sorted_dev, r.active = active_dev;
+  BeDeviceGuard guard(h->device);
+  if (int rc = be_launch_job_stats(r, stream)) return sss_fail(-30, std::string("job stats launch failed: ") + be_error(rc));
+  return 0;
+}
+
 extern "C" int sss_reset(sss_handle* h, const uint64_t* seeds_dev, const double* time_limits_dev, const uint8_t* mask_dev, void* stream) {
   if (!h || !seeds_dev) return sss_fail(-1, "NULL argument");
   if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
@@ -589,7 +607,8 @@ extern "C" int sss_decima_layer_lists(int num_envs, const sss_decima_lists* g, v
   return 0;
 }
 
-extern "C" int sss_decima_policy(sss_handle* h, const sss_decima_policy_args* g, void* stream) {
+// argmax: the arg-max instantiation of the same kernel (sss_decima_policy_argmax)
+static int sss_decima_policy_any(sss_handle* h, const sss_decima_policy_args* g, void* stream, bool argmax) {
   if (!h || !g) return sss_fail(-1, "NULL argument");
   if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
   BeDeviceGuard guard(h->device);
@@ -606,11 +625,14 @@ extern "C" int sss_decima_policy(sss_handle* h, const sss_decima_policy_args* g,
   d.rng_seed = g->rng_seed, d.rng_counter = g->rng_counter, d.stage_idx = g->stage_idx_dev, d.num_exec = g->num_exec_dev;
   d.stage_sel = g->stage_sel_dev, d.job_idx = g->job_idx_dev, d.exec_sel = g->exec_sel_dev, d.lgprob = g->lgprob_dev;
   d.stage_scores = g->stage_scores_dev, d.exec_scores = g->exec_scores_dev, d.prof = g->prof_dev;
-  if (int rc = be_launch_decima_policy(h->L, h->B, h->cfg.num_executors, d, stream)) return sss_fail(-30, std::string("decima policy launch failed: ") + be_error(rc));
+  if (int rc = argmax ? be_launch_decima_policy_argmax(h->L, h->B, h->cfg.num_executors, d, stream) : be_launch_decima_policy(h->L, h->B, h->cfg.num_executors, d, stream)) return sss_fail(-30, std::string("decima policy launch failed: ") + be_error(rc));
   return 0;
 }
 
-extern "C" int sss_decima_sample(int n_obs, int which, const sss_decima_sample_args* g, void* stream) {
+extern "C" int sss_decima_policy(sss_handle* h, const sss_decima_policy_args* g, void* stream) { return sss_decima_policy_any(h, g, stream, false); }
+extern "C" int sss_decima_policy_argmax(sss_handle* h, const sss_decima_policy_args* g, void* stream) { return sss_decima_policy_any(h, g, stream, true); }
+
+static int sss_decima_sample_any(int n_obs, int which, const sss_decima_sample_args* g, void* stream, bool argmax) {
   if (!g || n_obs < 1 || (which != 0 && which != 1)) return sss_fail(-1, "bad argument");
   if (g->num_executors < 1) return sss_fail(-28, "num_executors must be >= 1");
   SssDecimaSampleArgs d;
@@ -619,9 +641,12 @@ extern "C" int sss_decima_sample(int n_obs, int which, const sss_decima_sample_a
   d.obs_job_off = g->obs_job_off_dev, d.sched_rank = g->sched_rank_dev, d.node_job = g->node_job_dev, d.job_gid = g->job_gid_dev;
   d.stage_idx = g->stage_idx_dev, d.num_exec = g->num_exec_dev, d.stage_sel = g->stage_sel_dev, d.job_idx = g->job_idx_dev;
   d.exec_sel = g->exec_sel_dev, d.lgprob = g->lgprob_dev, d.any_stage = g->any_stage_dev;
-  if (int rc = be_launch_decima_sample(n_obs, which, d, stream)) return sss_fail(-30, std::string("decima sample launch failed: ") + be_error(rc));
+  if (int rc = argmax ? be_launch_decima_argmax(n_obs, which, d, stream) : be_launch_decima_sample(n_obs, which, d, stream))
+    return sss_fail(-30, std::string(argmax ? "decima argmax launch failed: " : "decima sample launch failed: ") + be_error(rc));
   return 0;
 }
+extern "C" int sss_decima_sample(int n_obs, int which, const sss_decima_sample_args* g, void* stream) { return sss_decima_sample_any(n_obs, which, g, stream, false); }
+extern "C" int sss_decima_argmax(int n_obs, int which, const sss_decima_sample_args* g, void* stream) { return sss_decima_sample_any(n_obs, which, g, stream, true); }
 
 extern "C" int sss_prefix_rows(const int32_t* src_dev, int64_t src_row_stride, int64_t src_col_stride, const uint8_t* mask_dev, int n_rows, int n_cols,
                                int64_t* off_dev, int64_t* cnt_dev, int64_t* totals_dev, void* stream) {

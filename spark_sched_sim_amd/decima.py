@@ -806,18 +806,21 @@ class DecimaPolicy(nn.Module):
 
     @torch.no_grad()
     def _sample_kernels(self, g: dict[str, Any], h: dict[str, torch.Tensor], padded: torch.Tensor, generator: torch.Generator | None,
-                        scores_out: dict | None = None, _stream: int | None = None) -> dict[str, torch.Tensor]:
+                        scores_out: dict | None = None, _stream: int | None = None, greedy: bool = False) -> dict[str, torch.Tensor]:
         """both draws on the device (include/sss.h sss_decima_sample): stage draw -> executor scores
         of the chosen stage's job -> executor-count draw; Gumbel-max over a counter-based stream
         (seed = the generator's, counter = number of calls so far).
+        `greedy`: both decisions by sss_decima_argmax instead (largest score, ties to the lowest index) - the same launches, and the
+        draw counter `_calls` stays where it is: an evaluation between two training iterations does not change the run's samples.
         On a capacity graph (`env.decima_graph_on_device`: act-and-forget inference, its buffers are overwritten by the next
         call anyway) the result tensors and the argument structure are kept and reused from call to call as well."""
         import ctypes
 
         from .binding import SssDecimaSampleArgs, device_of
         B, E, dev = g["n_obs"], self.num_executors, padded.device
-        self._calls = getattr(self, "_calls", 0) + 1
+        self._calls = getattr(self, "_calls", 0) + (0 if greedy else 1)
         seed = (generator.initial_seed() if generator is not None else 0) & (2 ** 64 - 1)
+        pick = self._kb.lib.sss_decima_argmax if greedy else self._kb.lib.sss_decima_sample
         key = (B, E, g["n_pad"], padded.data_ptr(), g["obs_nodes"].data_ptr(), g["obs_node_off"].data_ptr(), g["obs_job_off"].data_ptr(), g["sched_rank"].data_ptr(),
                g["node_job"].data_ptr())
         kept = self.__dict__.get("_sample_ws") if "totals_dev" in g else None
@@ -842,18 +845,18 @@ class DecimaPolicy(nn.Module):
         a.rng_seed, a.rng_counter = seed, self._calls
         if _stream is not None:  # (the caller has made the device current)
             stream = _stream
-            self._kb.check(self._kb.lib.sss_decima_sample(B, 0, ctypes.byref(a), stream))
+            self._kb.check(pick(B, 0, ctypes.byref(a), stream))
         else:
             stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
             with device_of(dev):
-                self._kb.check(self._kb.lib.sss_decima_sample(B, 0, ctypes.byref(a), stream))
+                self._kb.check(pick(B, 0, ctypes.byref(a), stream))
         self._launch("exec", B * E, self._packed[1]["exec"], _stream=_stream, w16=self._packed[1].get("exec16"), w2_16=self._packed[1].get("exec_mfma"), x=g["x"], h_dag=h["dag"], h_glob=h["glob"], out=es,
                      idx0=job_gid, job_obs=g["job_obs"], job_first=g["job_first"], job_cap=g["job_cap"])
         if _stream is not None:
-            self._kb.check(self._kb.lib.sss_decima_sample(B, 1, ctypes.byref(a), stream))
+            self._kb.check(pick(B, 1, ctypes.byref(a), stream))
         else:
             with device_of(dev):
-                self._kb.check(self._kb.lib.sss_decima_sample(B, 1, ctypes.byref(a), stream))
+                self._kb.check(pick(B, 1, ctypes.byref(a), stream))
         out["env_stage_idx"], out["env_num_exec"] = stage_idx, num_exec
         out["rng"] = (a.rng_seed, a.rng_counter)
         if scores_out is not None:
@@ -925,17 +928,19 @@ class DecimaPolicy(nn.Module):
         the policy keeps and the NEXT call on a graph of the same shape overwrites, like the observation buffers `env.step`
         returns. Consume them before the next call (the in-tree collector copies them on the stream) or pass
         `fresh_outputs=True` to get copies you own. Graphs with exact sizes (`env.decima_graph()`) return fresh tensors.
-        `greedy`: the most probable stage and executor count instead of a draw (evaluation; tensor-op path)."""
+        `greedy`: the stage and the executor count with the largest score instead of a draw (evaluation). It takes the same route
+        as sampling: with the kernels, sss_decima_argmax in place of the two draws (ties go to the lowest index; the draw counter
+        does not advance), else the tensor ops below."""
         B, N = g["n_obs"], g["n_pad"]
         M, J = g["x"].shape[0], g["job_obs"].numel()
-        if self._use_kernels(g) and M > 0 and J > 0 and not greedy:
+        if self._use_kernels(g) and M > 0 and J > 0:
             # (the stream handle and the current device are looked up once for the pass's seven library calls)
             from .binding import device_of
             dev = g["x"].device
             with device_of(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
                 h = self._encode_kernels(g, stream)
-                out = self._sample_kernels(g, h, self._stage_scores_kernels(g, h, stream, for_draw_only=True), generator, _stream=stream)
+                out = self._sample_kernels(g, h, self._stage_scores_kernels(g, h, stream, for_draw_only=True), generator, _stream=stream, greedy=greedy)
             return {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in out.items()} if fresh_outputs else out
         # tensor-op path (other architectures, graphs built without the graph kernel)
         h = self.encode(g)
@@ -961,13 +966,14 @@ class DecimaPolicy(nn.Module):
 
     @torch.no_grad()
     def act_env(self, env, counter: int, seed: int = 0, active: torch.Tensor | None = None, want_scores: bool = False,
-                want_prof: bool = False):
+                want_prof: bool = False, greedy: bool = False):
         """Decima's decision for every env of a `VecSparkSchedSimEnv` in ONE kernel launch
         (include/sss.h sss_decima_policy): transform, GNN, scores and both draws per env inside one
         wavefront, no intermediate graph, no host sync. Slower than the row-parallel pipeline at large
         batches (see `schedule_env`); useful when launches / syncs dominate. Returns (actions for `env.step`, the `act`
         dict [+ "stage_scores" f32[B,node_cap], "exec_scores" f32[B,E] with `want_scores`]). The draws
-        are a deterministic function of (seed, counter, env): pass a new `counter` every step."""
+        are a deterministic function of (seed, counter, env): pass a new `counter` every step. `greedy`: the kernel's arg-max
+        instantiation (sss_decima_policy_argmax) - both decisions are the largest score, seed and counter are ignored."""
         import ctypes
 
         from .binding import SssDecimaPolicyArgs
@@ -1001,7 +1007,7 @@ class DecimaPolicy(nn.Module):
         if want_prof:  # shader cycles per phase: analysis, prep, layers, summaries, stage, exec; then depth, nodes
             out["prof"] = torch.zeros((B, 8), dtype=torch.int64, device=dev)
             a.prof_dev = out["prof"].data_ptr()
-        self._kb.check(self._kb.lib.sss_decima_policy(env._h, ctypes.byref(a), env._stream()))
+        self._kb.check((self._kb.lib.sss_decima_policy_argmax if greedy else self._kb.lib.sss_decima_policy)(env._h, ctypes.byref(a), env._stream()))
         out.update(stage_sel=ws["stage_sel"].long(), job_idx=ws["job_idx"].long(), exec_sel=ws["exec_sel"].long(), lgprob=ws["lgprob"],
                    any_stage=ws["stage_idx"] >= 0)
         return {"stage_idx": ws["stage_idx"], "num_exec": ws["num_exec"]}, out
@@ -1028,19 +1034,19 @@ class DecimaPolicy(nn.Module):
 
         OWNERSHIP: by default both are views of work space that the next `schedule_env` / `act` call on this policy overwrites (see
         `act`): hand the actions to `env.step` and read `aux["lgprob"]` etc. before calling again, or pass `fresh_outputs=True` for
-        tensors you may keep (a rollout recorder of your own, logging). `greedy`: arg-max actions instead of sampled ones."""
+        tensors you may keep (a rollout recorder of your own, logging). `greedy`: arg-max actions instead of sampled ones, by the same
+        route (`one_launch` included) and without advancing the draw counter."""
         if getattr(self, "_kb", None) is None:
             self.bind_kernels(env._b)
-        if greedy:
-            a = self.act(env.decima_graph(active), generator, greedy=True)
-            return self.env_actions(a), a
+        if one_launch and greedy:  # (the draw counter stays: greedy calls leave the sampled stream alone)
+            return self.act_env(env, 0, active=active, greedy=True)
         if one_launch:
             self._calls = getattr(self, "_calls", 0) + 1
             return self.act_env(env, self._calls, seed=generator.initial_seed() if generator is not None else 0, active=active)
         # no device->host round trip when the graph kernel and the GNN kernels can do the whole step (the graph's totals stay on
         # the device); else the graph with exact sizes (one read-back of its totals)
         on_dev = host_sync is False or (host_sync is None and self._use_kernels() and env.graph_kernel_fits)
-        a = self.act(env.decima_graph_on_device(active) if on_dev else env.decima_graph(active, reuse_buffers=True), generator, fresh_outputs=fresh_outputs)
+        a = self.act(env.decima_graph_on_device(active) if on_dev else env.decima_graph(active, reuse_buffers=True), generator, greedy=greedy, fresh_outputs=fresh_outputs)
         return self.env_actions(a), a
 
     @torch.no_grad()

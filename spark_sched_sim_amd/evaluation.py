@@ -1,0 +1,110 @@
+"""Evaluating schedulers on held-out job sequences: whole episodes of every env of a `VecSparkSchedSimEnv` under an on-device
+heuristic or a `DecimaPolicy`, the per-env episode metrics from one kernel launch (`env.job_stats`, include/sss.h sss_job_stats),
+and the paired comparison of several schedulers on the same seeds (the reference's one published comparison, README.md:5-7 with
+examples.py:84-102). `tools/decima_vs_fair.py`, `tools/heuristic_baselines.py` and `training.Trainer` (`eval_every`) use it."""
+from __future__ import annotations
+
+from typing import Any, Sequence
+
+import torch
+
+from .binding import JOB_STATS_COLUMNS
+
+DECISION_CHECK_EVERY = 64  # Decima-in-the-loop steps between two reads of the done mask (one device->host sync each)
+
+
+def _summarize(env, q: Sequence[float]) -> dict[str, torch.Tensor]:
+    r = env.job_stats(q, want_sorted=True)
+    out = {name: r["stats"][:, k].clone() for k, name in enumerate(JOB_STATS_COLUMNS)}
+    out["avg_job_duration_s"] = out["avg_completed_job_duration"]  # (the tools' key: the reference's env.avg_job_duration)
+    # ... and the episode's own mean job duration in seconds: the ring outlives reset() (as the reference's job_duration_buff does), so on
+    # an env that played other episodes before and holds fewer than 200 jobs per episode the column above averages those in
+    out["episode_avg_job_duration_s"] = out["avg_job_duration"] * 1e-3
+    out["pct"], out["sorted"] = r["pct"].clone(), r["sorted"].clone()
+    out["q"] = torch.tensor([float(x) for x in q], dtype=torch.float64)
+    out["ok"] = ((env.header_field("terminated") != 0) & (env.obs_i32[:, 7] == 0)).clone()
+    out["steps"] = env.header_field("ep_steps").clone()  # step() calls of the episode
+    return out
+
+
+@torch.no_grad()
+def run_episodes(env, actor, seed, max_steps: int = 200_000, *, param: int = 0, greedy: bool = False, generator: torch.Generator | None = None,
+                 q: Sequence[float] = (25, 50, 75, 100), chunk: int = 200) -> dict[str, torch.Tensor]:
+    """every env of `env` (no auto-reset) plays one whole episode from `reset(seed=seed)` under `actor`:
+      - the name of an on-device policy ("fair", "fifo", "wfair", "sjfcp", "hash") with `param`: fused `env.rollout` launches of
+        `chunk` steps, the done mask read after each;
+      - a `DecimaPolicy` (`greedy`: arg-max actions - they leave the policy's draw counter alone; else draws from `generator`):
+        policy and step launches in lock step, finished or failed envs sit the remaining launches out (SSS_SKIP_ENV), the done
+        mask read every 64 steps.
+    At most `max_steps` steps per env. Returns per-env DEVICE tensors the caller owns: the columns of `env.job_stats`
+    (`binding.JOB_STATS_COLUMNS`; `avg_job_duration_s` = the mean over the last <= 200 completed jobs in seconds), `pct` f64[B, len(q)]
+    with `q`, `sorted` (the env's sorted job durations, NaN behind them), `ok` (the episode ended without an env error) and `steps`."""
+    from .training import SKIP_ENV
+
+    B, dev = env.num_envs, env.device
+    if env.auto_reset:
+        raise ValueError("run_episodes: the env must not auto-reset (a finished episode's statistics are read from its arena block)")
+    env.reset(seed=seed)
+    if isinstance(actor, str):
+        for _ in range(max(1, -(-int(max_steps) // int(chunk)))):
+            env.rollout(actor, int(chunk), param)
+            if bool(((env.header_field("terminated") != 0) | (env.obs_i32[:, 7] != 0)).all()):
+                break
+        return _summarize(env, q)
+    done = torch.zeros(B, dtype=torch.bool, device=dev)
+    skip = torch.full((B,), SKIP_ENV, dtype=torch.int32, device=dev)
+    t = 0
+    while t < max_steps:
+        for _ in range(DECISION_CHECK_EVERY):
+            act, _ = actor.schedule_env(env, generator=generator, active=~done, greedy=greedy)
+            env.step_async(torch.where(done, skip, act["stage_idx"]).contiguous(), act["num_exec"])
+            done = done | (env.obs_i32[:, 6] != 0) | (env.obs_i32[:, 7] != 0)
+            t += 1
+        if bool(done.all()):
+            break
+    return _summarize(env, q)
+
+
+def _ci95(v: torch.Tensor, n: int) -> float:
+    return float(1.96 * v.std() / n ** 0.5)
+
+
+def pooled_percentiles(sorted_rows: torch.Tensor, q: Sequence[float]) -> list[float]:
+    """percentiles (linear interpolation, as numpy's default) of ALL the job durations in `sorted_rows` f64[n, job_cap] (NaN = no job)"""
+    v = sorted_rows.reshape(-1)
+    v = v[~torch.isnan(v)].sort().values
+    n = v.numel()
+    if n == 0:
+        return [float("nan")] * len(q)
+    pos = torch.tensor([float(x) for x in q], dtype=torch.float64, device=v.device) / 100.0 * (n - 1)
+    lo = pos.floor().long().clamp(0, n - 1)
+    hi = (lo + 1).clamp(max=n - 1)
+    g = pos - lo.to(torch.float64)
+    return (v[lo] + (v[hi] - v[lo]) * g).tolist()
+
+
+def compare(results: dict[str, dict[str, torch.Tensor]], baseline: str = "fair", metric: str = "avg_job_duration_s") -> dict[str, Any]:
+    """mean / 95 % confidence interval per scheduler over the envs where EVERY scheduler finished its episode without error (a sampled
+    action sequence can run into the reference's own "[step]" stall), the paired difference to `baseline` (key
+    `minus_<baseline>_s`), and the percentiles of the job durations pooled over those envs (`job_duration_percentiles`, in the
+    simulator's time unit, with the per-env percentiles' mean beside them). `metric`: the per-env figure compared under the key
+    `avg_job_duration_s` - `run_episodes`' `avg_job_duration_s` (the reference's env.avg_job_duration) or `episode_avg_job_duration_s`
+    (for envs that are reused from one evaluation to the next)"""
+    ok = None
+    for r in results.values():
+        ok = r["ok"] if ok is None else ok & r["ok"]
+    n = int(ok.sum())
+    out: dict[str, Any] = {"envs_compared": n, "envs_excluded": int((~ok).sum()), "metric": metric}
+    base = results[baseline][metric][ok]
+    for name, r in results.items():
+        v = r[metric][ok]
+        d = v - base
+        row = {"avg_job_duration_s": float(v.mean()), "ci95": _ci95(v, n), "avg_num_jobs": float(r["avg_num_jobs"][ok].mean()),
+               "steps_per_episode": float(r["steps"][ok].double().mean()),
+               f"minus_{baseline}_s": float(d.mean()), f"minus_{baseline}_ci95": _ci95(d, n),
+               f"envs_better_than_{baseline}": float((d < 0).double().mean())}
+        if "sorted" in r:
+            qs = r["q"].tolist()
+            row["job_duration_percentiles"] = {"q": qs, "pooled": pooled_percentiles(r["sorted"][ok], qs), "mean_over_envs": r["pct"][ok].mean(0).tolist()}
+        out[name] = row
+    return out

@@ -28,3 +28,21 @@ def avg_num_jobs(env, i: int | None = None):
 
 def job_duration_percentiles(env, i: int | None = None):
     return np.percentile(job_durations(env, i), [25, 50, 75, 100])
+
+
+# ---- the same for every env of a `VecSparkSchedSimEnv` at once: device tensors from one kernel launch (`env.job_stats`, include/sss.h
+# sss_job_stats), bit for bit the values of the functions above on env i, with no device->host copy
+
+def batch_job_duration_percentiles(env, q=(25, 50, 75, 100)):
+    """f64[B, len(q)]: row i = np.percentile(job_durations(env, i), q)"""
+    return env.job_stats(q)["pct"]
+
+
+def batch_avg_num_jobs(env):
+    """f64[B]: entry i = avg_num_jobs(env, i) (NaN where that raises: wall_time == 0)"""
+    return env.job_stats(())["stats"][:, 3]
+
+
+def batch_avg_job_duration(env):
+    """f64[B]: entry i = avg_job_duration(env, i) (NaN for an env without arrivals)"""
+    return env.job_stats(())["stats"][:, 2]

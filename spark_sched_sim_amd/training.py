@@ -899,6 +899,41 @@ class Trainer:
                                           policy=self.policy, generator=gen, on_env_error=train_cfg.get("on_env_error", "raise"))
         self.ppo = PPO(self.policy, train_cfg, generator=gen)
         self.history: list[dict[str, float]] = []
+        # evaluation on held-out job sequences while training (off by default): every `eval_every` iterations `eval_envs` whole
+        # episodes from `eval_seed` on an env of its own, under the policy (`eval_greedy`: arg-max actions) and under fair
+        self.eval_every = int(train_cfg.get("eval_every", 0) or 0)
+        self.eval_envs = int(train_cfg.get("eval_envs", 64))
+        self.eval_seed = int(train_cfg.get("eval_seed", 10_000_000))
+        self.eval_greedy = bool(train_cfg.get("eval_greedy", True))
+        self.eval_history: list[dict[str, Any]] = []
+        self._eval = None
+        self._eval_env_args = dict(env_cfg=sim_cfg, device=dev, _lib=_lib, pack=pack)
+
+    def evaluate(self, tag: int | None = None) -> dict[str, Any]:
+        """`eval_envs` held-out job sequences (seeds from `eval_seed`) played to their end under the current policy and under the fair
+        scheduler on the trainer's evaluation env (created at the first call, fair's episodes played once): the paired summary of
+        `evaluation.compare` over each episode's own mean job duration. Leaves the training run as it found it: the policy's draw
+        counter, its training mode and the collector's generator are not touched (sampled evaluation draws from a generator of its own)."""
+        from .evaluation import compare, run_episodes
+        from .vec_env import VecSparkSchedSimEnv
+
+        if self._eval is None:
+            a = self._eval_env_args
+            env = VecSparkSchedSimEnv(a["env_cfg"], self.eval_envs, device=a["device"], _lib=a["_lib"], pack=a["pack"])
+            gen = torch.Generator(device=self.device if self.device.type == "cuda" else "cpu")
+            gen.manual_seed(self.eval_seed)
+            self._eval = {"env": env, "gen": gen, "fair": run_episodes(env, "fair", self.eval_seed)}
+        ev = self._eval
+        was_training, calls = self.policy.training, getattr(self.policy, "_calls", 0)
+        self.policy.eval()
+        try:
+            res = {"fair": ev["fair"], "decima": run_episodes(ev["env"], self.policy, self.eval_seed, greedy=self.eval_greedy, generator=ev["gen"])}
+        finally:
+            self.policy._calls = calls
+            self.policy.train(was_training)
+        row = compare(res, metric="episode_avg_job_duration_s")
+        row["after_iterations"], row["greedy"] = tag, self.eval_greedy
+        return row
 
     def _gather_stats(self, stats: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
         import torch.distributed as dist
@@ -951,12 +986,16 @@ class Trainer:
             rec = dict(learn, iteration=i, avg_num_jobs=float(avg_num_jobs), samples=int(ro.active.sum()), env_errors=self.collector.env_errors,
                        episode_length=float(ro.lengths.float().mean()))
             self.history.append(rec)
+            if self.eval_every and (i + 1) % self.eval_every == 0 and self.rank == 0:
+                self.eval_history.append(self.evaluate(i + 1))
             if verbose and self.rank == 0:
                 print(f"Iteration {i + 1} complete. Avg. # jobs: {avg_num_jobs:.3f}", flush=True)
         return self.history
 
     def close(self) -> None:
         self.env.close()
+        if self._eval is not None:
+            self._eval["env"].close()
 
 
 def make_trainer(cfg: dict[str, Any], device: str | torch.device | None = None, _lib=None) -> Trainer:

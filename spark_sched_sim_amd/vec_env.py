@@ -635,6 +635,37 @@ class VecSparkSchedSimEnv:
         return {"avg_job_duration": ring_sum / n_ring * 1e-3, "avg_num_jobs": dur.sum(1) / wall, "num_completed_jobs": done,
                 "num_job_arrivals": done + act}
 
+    def job_stats(self, q: Sequence[float] = (25, 50, 75, 100), active: torch.Tensor | None = None, want_sorted: bool = False) -> dict[str, torch.Tensor]:
+        """the episode metrics of ALL envs from one kernel launch (include/sss.h sss_job_stats, where every column is defined), as
+        device tensors and with no device->host transfer: `stats` f64[B, 8] - columns `binding.JOB_STATS_COLUMNS`: the number of
+        arrived jobs, the sum and the mean of their durations (metrics.py:4-14), `avg_num_jobs` (:16-18), the mean duration of the
+        last <= 200 completed jobs in seconds (spark_sched_sim.py:243-245), completed jobs, active jobs, wall time - `pct` f64[B, len(q)] =
+        `numpy.percentile(durations, q)` and, with `want_sorted`, `sorted` f64[B, job_cap] (the sorted durations, NaN behind them).
+        Every value carries the bits of the host functions of `metrics` on env i. `active` (bool / u8 [B]): rows of envs with 0 keep
+        what they held. The percent tensor and the outputs are kept per `q` and overwritten by the next call with the same `q`."""
+        from .binding import JOB_STATS_MAX_Q
+        qs = tuple(float(x) for x in q)
+        if len(qs) > JOB_STATS_MAX_Q:
+            raise ValueError(f"job_stats: at most {JOB_STATS_MAX_Q} percent values, got {len(qs)}")
+        if not all(0.0 <= x <= 100.0 for x in qs):  # (also refuses NaN)
+            raise ValueError("job_stats: percentiles must be in the range [0, 100]")
+        B, dev, nq = self.num_envs, self.device, len(qs)
+        cache = self.__dict__.setdefault("_job_stats_ws", {})
+        ws = cache.get(qs)
+        if ws is None:
+            ws = cache[qs] = {"q": torch.tensor(qs, dtype=torch.float64).to(dev) if nq else None,
+                              "stats": torch.zeros((B, 8), dtype=torch.float64, device=dev),
+                              "pct": torch.zeros((B, nq), dtype=torch.float64, device=dev)}
+        if want_sorted and "sorted" not in ws:
+            ws["sorted"] = torch.full((B, self.dims.job_cap), float("nan"), dtype=torch.float64, device=dev)
+        act8 = _mask_u8(active)
+        self._b.check(self._b.lib.sss_job_stats(self._h, nq, ws["q"].data_ptr() if nq else None, ws["stats"].data_ptr(), ws["pct"].data_ptr() if nq else None,
+                                                ws["sorted"].data_ptr() if want_sorted else None, act8.data_ptr() if act8 is not None else None, self._stream()))
+        out = {"stats": ws["stats"], "pct": ws["pct"]}
+        if want_sorted:
+            out["sorted"] = ws["sorted"]
+        return out
+
     def counters(self) -> dict[str, int]:
         """lifetime totals over all envs: real step() calls, events popped, SURVEY 8(d) model bytes"""
         hdr = self._env_view[:, : self.dims.hdr_bytes].cpu().numpy()

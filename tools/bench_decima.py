@@ -34,6 +34,9 @@ def main():
     ap.add_argument("--shards", type=int, default=1, help="split the envs into sub-batches on separate HIP streams (one shard's "
                     "step-kernel tail overlaps the other shards' GNN kernels)")
     ap.add_argument("--one-launch", action="store_true", help="per-env policy kernel (sss_decima_policy) instead of the row-parallel pipeline")
+    ap.add_argument("--greedy", action="store_true", help="arg-max actions (sss_decima_argmax / sss_decima_policy_argmax) instead of draws: the evaluation step")
+    ap.add_argument("--executors", type=int, default=10)
+    ap.add_argument("--jobs", type=int, default=50)
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--device-index", type=int, default=None)
     a = ap.parse_args()
@@ -46,13 +49,13 @@ def main():
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group(a.dist_backend)
-    cfg = dict(num_executors=10, job_arrival_cap=50, job_arrival_rate=4.0e-5, moving_delay=2000.0, warmup_delay=1000.0)
+    cfg = dict(num_executors=a.executors, job_arrival_cap=a.jobs, job_arrival_rate=4.0e-5, moving_delay=2000.0, warmup_delay=1000.0)
     S = max(1, a.shards)
     assert a.envs % S == 0
     envs = [VecSparkSchedSimEnv(cfg, a.envs // S, device=dev, auto_reset=True, seed_stride=a.envs * world) for _ in range(S)]
     streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
     torch.manual_seed(0)
-    policy = DecimaPolicy(num_executors=10, **AGENT).to(dev).eval()
+    policy = DecimaPolicy(num_executors=a.executors, **AGENT).to(dev).eval()
     gens = [torch.Generator(device=dev).manual_seed(1 + k + 1000 * rank) for k in range(S)]
     for k, e in enumerate(envs):
         e.reset(seed=rank * a.envs + k * (a.envs // S))
@@ -65,7 +68,7 @@ def main():
             t0 = time.perf_counter()
         for e, st, gen in zip(envs, streams, gens):
             with torch.cuda.stream(st):
-                act, _ = policy.schedule_env(e, generator=gen, one_launch=a.one_launch)
+                act, _ = policy.schedule_env(e, generator=gen, one_launch=a.one_launch, greedy=a.greedy)
                 e.step(act)
     torch.cuda.synchronize()
     if world > 1:
@@ -82,7 +85,7 @@ def main():
         err = int(e_t)
     if rank == 0:
         print(json.dumps({"metric": "env-steps/s with Decima in the loop", "value": world * a.envs * a.steps / dt, "n_gpus": world, "envs_per_gpu": a.envs,
-                          "ms_per_step": 1e3 * dt / a.steps, "shards": S, "one_launch": a.one_launch, "err_envs": err}))
+                          "ms_per_step": 1e3 * dt / a.steps, "shards": S, "one_launch": a.one_launch, "greedy": a.greedy, "executors": a.executors, "jobs": a.jobs, "err_envs": err}))
     if world > 1:
         dist.destroy_process_group()
 

@@ -23,7 +23,8 @@ import torch
 
 sys.path.insert(0, osp.dirname(osp.dirname(osp.abspath(__file__))))
 from spark_sched_sim_amd import VecSparkSchedSimEnv, workload  # noqa: E402
-from spark_sched_sim_amd.training import SKIP_ENV, Trainer  # noqa: E402
+from spark_sched_sim_amd.evaluation import compare, run_episodes  # noqa: E402,F401
+from spark_sched_sim_amd.training import Trainer  # noqa: E402
 
 AGENT = dict(agent_cls="DecimaScheduler", embed_dim=16,
              gnn_mlp_kwargs=dict(hid_dims=[32, 16], act_cls="LeakyReLU", act_kwargs=dict(negative_slope=0.2)),
@@ -32,55 +33,11 @@ AGENT = dict(agent_cls="DecimaScheduler", embed_dim=16,
 
 def episodes_under_decima(env, policy, seed0: int, greedy: bool, gen) -> dict:
     """every env plays one whole episode under the policy; finished (or failed) envs sit the remaining launches out"""
-    B, dev = env.num_envs, env.device
-    env.reset(seed=seed0)
-    done = torch.zeros(B, dtype=torch.bool, device=dev)
-    skip = torch.full((B,), SKIP_ENV, dtype=torch.int32, device=dev)
-    steps = 0
-    while True:
-        for _ in range(64):
-            act, _ = policy.schedule_env(env, generator=gen, active=~done, greedy=greedy)
-            env.step_async(torch.where(done, skip, act["stage_idx"]).contiguous(), act["num_exec"])
-            done = done | (env.obs_i32[:, 6] != 0) | (env.obs_i32[:, 7] != 0)
-            steps += 1
-        if bool(done.all()) or steps > 200_000:
-            break
-    return summarize(env)
+    return run_episodes(env, policy, seed0, greedy=greedy, generator=gen)
 
 
 def episodes_under_heuristic(env, name: str, seed0: int) -> dict:
-    env.reset(seed=seed0)
-    for _ in range(2000):
-        env.rollout(name, 200)
-        if bool(((env.header_field("terminated") != 0) | (env.obs_i32[:, 7] != 0)).all()):
-            break
-    return summarize(env)
-
-
-def summarize(env) -> dict:
-    st = env.rollout_stats()
-    ok = (env.header_field("terminated") != 0) & (env.obs_i32[:, 7] == 0)
-    return {"avg_job_duration_s": st["avg_job_duration"].clone(), "ok": ok.clone(), "avg_num_jobs": st["avg_num_jobs"].clone(),
-            "steps": env.header_field("ep_steps").clone()}
-
-
-def compare(results: dict) -> dict:
-    """mean / CI per policy over the envs where EVERY policy finished its episode without error (a sampled action sequence can run
-    into the reference's own "[step]" stall), and the paired difference to fair"""
-    ok = None
-    for r in results.values():
-        ok = r["ok"] if ok is None else ok & r["ok"]
-    n = int(ok.sum())
-    out = {"envs_compared": n, "envs_excluded": int((~ok).sum())}
-    fair = results["fair"]["avg_job_duration_s"][ok]
-    for name, r in results.items():
-        v = r["avg_job_duration_s"][ok]
-        d = v - fair
-        out[name] = {"avg_job_duration_s": float(v.mean()), "ci95": float(1.96 * v.std() / n ** 0.5), "avg_num_jobs": float(r["avg_num_jobs"][ok].mean()),
-                     "steps_per_episode": float(r["steps"][ok].double().mean()),
-                     "minus_fair_s": float(d.mean()), "minus_fair_ci95": float(1.96 * d.std() / n ** 0.5),
-                     "envs_better_than_fair": float((d < 0).double().mean())}
-    return out
+    return run_episodes(env, name, seed0, max_steps=400_000)
 
 
 def main():

@@ -24,7 +24,8 @@ ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, osp.join(ROOT, "tools"))
 from spark_sched_sim_amd import VecSparkSchedSimEnv, workload  # noqa: E402
-from decima_vs_fair import AGENT, compare, episodes_under_decima, summarize  # noqa: E402
+from spark_sched_sim_amd.evaluation import compare, run_episodes  # noqa: E402
+from decima_vs_fair import AGENT, episodes_under_decima  # noqa: E402
 
 CONFIGS = {
     "c1": dict(num_executors=10, job_arrival_cap=50, job_arrival_rate=4.0e-5, moving_delay=2000.0, warmup_delay=1000.0),
@@ -41,12 +42,7 @@ def policies(alphas) -> list[tuple[str, str, int]]:
 
 
 def episodes(env, policy: str, param: int, seed0: int, launch_steps: int = 200) -> dict:
-    env.reset(seed=seed0)
-    for _ in range(5000):
-        env.rollout(policy, launch_steps, param)
-        if bool(((env.header_field("terminated") != 0) | (env.obs_i32[:, 7] != 0)).all()):
-            break
-    return summarize(env)
+    return run_episodes(env, policy, seed0, max_steps=5000 * launch_steps, param=param, chunk=launch_steps)
 
 
 def steps_per_second(env, policy: str, param: int, seed0: int, launch_steps: int, launches: int, timed: bool) -> float:
