@@ -668,6 +668,11 @@ class DecimaPolicy(nn.Module):
         x = g["x"]
         dev = x.device
         M, J, B = x.shape[0], g["job_obs"].numel(), g["n_obs"]
+        if M == 0 and J == 0:
+            # an exact-size graph without a node (every env finished, no auto-reset): its arrays are empty, and an empty array's
+            # pointer is passed as NULL - nothing to launch. The sums over no job are zero, as the tensor-op forward gives them.
+            z = lambda n: torch.zeros((n, 16), dtype=torch.float32, device=dev)  # noqa: E731
+            return {"node": z(0), "dag": z(0), "glob": z(B)}
         if "max_depth" in g and "layer_cnt" in g and 0 <= g["max_depth"] <= 32:
             return self._encode_one_call(g, w, _stream)
         h_init = torch.empty((M, 16), dtype=torch.float32, device=dev)
@@ -796,6 +801,8 @@ class DecimaPolicy(nn.Module):
             rows = min(rows, g["sched_list"].numel())
         else:
             out = torch.full((g["n_obs"], g["n_pad"]), float("-inf"), dtype=torch.float32, device=g["x"].device)
+            if M == 0:  # (no node, so no schedulable stage: every slot stays -inf)
+                return out
             if "sched_list" in g:  # the graph kernel's list of the schedulable nodes: exactly the rows to score (layer=1: no padding)
                 rows, idx0, exact = g["sched_list"].numel(), g["sched_list"], 1
             else:
@@ -870,6 +877,8 @@ class DecimaPolicy(nn.Module):
     def _exec_scores_kernels(self, g: dict[str, Any], h: dict[str, torch.Tensor], job_gid: torch.Tensor) -> torch.Tensor:
         k, E = job_gid.numel(), self.num_executors
         out = torch.empty((k, E), dtype=torch.float32, device=job_gid.device)
+        if k == 0:  # (no job asked for, e.g. a graph of finished envs only)
+            return out
         self._launch("exec", k * E, self._packed[1]["exec"], w16=self._packed[1].get("exec16"), w2_16=self._packed[1].get("exec_mfma"), x=g["x"], h_dag=h["dag"], h_glob=h["glob"], out=out,
                      idx0=job_gid.contiguous(), job_obs=g["job_obs"], job_first=g["job_first"], job_cap=g["job_cap"])
         return out

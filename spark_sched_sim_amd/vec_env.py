@@ -364,7 +364,9 @@ class VecSparkSchedSimEnv:
         ws = getattr(self, "_dg_dev", None)
         if ws is None:
             Mc, Ec, Jc = B * d.node_cap, B * d.edge_cap, B * d.job_cap
-            e = lambda n, dt, *tail: torch.empty((max(n, 1), *tail), dtype=dt, device=dev)  # noqa: E731
+            # (zeros, not uninitialised memory: for an env without a schedulable stage the executor-score launch reads the row of job 0 -
+            # `job_first`, `job_obs`, `job_cap` - and that row is not written when the very first graph built here has no job at all)
+            e = lambda n, dt, *tail: torch.zeros((max(n, 1), *tail), dtype=dt, device=dev)  # noqa: E731
             ws = self._dg_dev = {
                 "x": e(Mc, torch.float32, 5), "node_obs": e(Mc, torch.int64), "node_loc": e(Mc, torch.int64), "node_job": e(Mc, torch.int64),
                 "sched_rank": e(Mc, torch.int64), "gen": e(Mc, torch.int32), "node_recv": e(Mc, torch.int32), "stage_mask": e(Mc, torch.bool),

@@ -1,0 +1,83 @@
+"""Decima's inference forward pass on the MI355X - the product library's matrix-core forms (with the heads' exp / rcp based tanh) and
+the `vecforms` test build's vector-unit forms, each on its own - against the same forward pass in fp64 on the CPU
+(inference_fp64_util): every route of `DecimaPolicy` to an embedding or a score, tolerances from the fp32 tensor-op form's own error
+against fp64 measured in the same run; the measured tables are in profiles/inference_fp64.md."""
+import pytest
+
+import inference_fp64_util as U
+from decima_util import SCORE_ATOL
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+BUILDS = ("mfma", "vecforms")
+
+
+@pytest.fixture(scope="module")
+def prepared():
+    """(case, build) -> (env, unbound policy, graph, fp64 forward pass, fp32 tensor-op forward pass on the GPU): one env per case and
+    build, the references made once per case (both builds' envs show the same graph) with the input conditions checked on them"""
+    cache = {}
+
+    def get(case, build="mfma"):
+        if (case, "mfma") not in cache:
+            cache[case, "mfma"] = U.prepare(case, DEV)
+        if (case, build) not in cache:
+            from gpu_variant import load_variant
+            _, pol, g0, ref, top = cache[case, "mfma"]
+            env = U.open_env(case, DEV, load_variant(build))
+            g = env.decima_graph()
+            assert U.same_graph(g, g0)
+            cache[case, build] = (env, pol, g, ref, top)
+        return cache[case, build]
+    yield get
+    for env, *_ in cache.values():
+        env.close()
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("case", list(U.CASES))
+def test_kernel_routes_match_the_fp64_forward_pass(prepared, case, build):
+    """embeddings, job and observation summaries (relative to max(1, largest entry)), stage scores and executor scores (absolute, the
+    -inf pattern equal) of every route within the bound of `inference_fp64_util.bounds_of`; every route was the one it claims to be"""
+    env, pol, g, ref, top = prepared(case, build)
+    failures, rows = U.run_case(case, env, U.bind(pol, env), ref, top, g, U.arithmetic_terms(build, case, pol, g, ref))
+    print(f"{case}, {build}\n{U.table(rows)}")
+    assert not failures, failures
+    skipped = {r[0] for r in rows if r[4] is None}
+    assert skipped == U.expected_skips(case, g, one_launch_kernel=build == "mfma"), skipped
+
+
+@pytest.mark.parametrize("case", ["all_done", "all_done6"])
+def test_a_graph_without_a_node_gives_no_action_on_every_route(prepared, case):
+    """every env finished, no auto-reset: `act` on the exact-size graph (kernels bound, and tensor ops alone), `schedule_env` on the
+    exact-size and on the capacity graph and `act_env` agree - no stage anywhere, the action `env.step` takes for "nothing to schedule"""
+    env, pol, g, ref, top = prepared(case)
+    U.check_no_node_routes(env, pol, ref)
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("case", U.DECISION_CASES)
+def test_greedy_decisions_are_the_fp64_arg_max(prepared, case, build):
+    """`schedule_env(greedy=True)`, pipeline and one launch: stage and executor count equal the arg-max of the fp64 scores on every
+    observation whose fp64 lead exceeds twice the case's bound; at most 5 % of the observations with a choice are such near-ties"""
+    env, pol, g, ref, top = prepared(case, build)
+    bound, _, failures = U.bounds_of(ref, top)
+    assert not failures, failures
+    n = U.check_decisions(env, U.bind(pol, env), g, ref, bound)
+    print(case, build, n)
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("case", ["small16", "one_env"])
+@pytest.mark.parametrize("control", list(U.CONTROLS))
+def test_the_comparison_fails_a_subtly_wrong_forward_pass(prepared, case, control, build):
+    """negative controls: a Python entry point hands on a slightly wrong value (a bias entry of one weight image off by 1e-5, a child's
+    message left out, a job's sum one node short, two feature columns swapped for the heads, the count feature one count on) -
+    `compare` must report it. The first one stays under the 2e-5 of the older tests: they would not have seen it."""
+    env, pol, g, ref, top = prepared(case, build)
+    failures, rows = U.run_control(control, case, env, pol, g, ref, top)
+    print(control, len(failures), failures[:3], U.worst(rows))
+    assert failures
+    if control == "update_image_last_bias_plus_1e-5":
+        assert all(r[3] <= SCORE_ATOL for r in rows if r[4] is not None), U.worst(rows)
