@@ -815,6 +815,65 @@ int sss_timeline_render(sss_handle* h, const struct sss_timeline_render_args* a,
 int sss_job_stats(sss_handle* h, int n_q, const double* q_dev, double* stats_dev, double* pct_dev, double* sorted_dev, const uint8_t* active_dev,
                   void* stream);
 
+/* Copies of running environments: what `copy.deepcopy(env)` is for the reference's SparkSchedSimEnv (every field that
+ * spark_sched_sim/spark_sched_sim.py:34-125 sets up and an episode changes - the clock, the event queue, executors with their
+ * histories, jobs, the executor tracker's pools and commitments, the sampler's generator, the duration deque - plus the last
+ * observation). n env IMAGES go from a source STORE to a destination store in one launch, one workgroup per pair
+ * (src_ids_dev[k] -> dst_ids_dev[k], i32[n] each). A store is the set of per-env buffers an env lives in: a state arena of
+ * env_stride-byte blocks, the six observation buffers of sss_buffers and, optionally, the three timeline arrays of sss_timeline,
+ * each with num_slots rows. A NULL store stands for the buffers bound to the handle (with its bound timeline, if any), so the
+ * same call is
+ *   fork      src_store = dst_store = NULL: env -> env in one handle
+ *   snapshot  dst_store = slots the caller allocated (sized by sss_dims; state_dev 256-byte aligned)
+ *   restore   src_store = such slots - also ones filled from ANOTHER handle of the same layout
+ * layout_id is the sss_env_layout_id of the handle a caller's store was filled by (or sized for): the layout of an env's block -
+ * executor, job, stage, level, node and edge capacities, every offset, the block size, the kernel instantiation - and the workload
+ * pack (job records hold indices into it), hashed; num_envs is not part of it. A store whose id differs from the handle's is refused with -51: images only exist between equal layouts.
+ * An image is
+ *   - the block of the arena except (a) the table slots, in the pool overflow area, of pools whose record says the table has 8
+ *     entries - those slots are never interpreted - and (b) the destination's lifetime counters n_steps, n_events, model_bytes,
+ *     prof[5], n_fast, n_batched, n_rounds, which stay the destination's (sums over a store do not change). Everything else
+ *     is the source's: a step cut at its event budget (sss_step_bounded) goes on in the copy, err / err_line, the episode counters
+ *     and the episode's seed (an auto-reset of the copy therefore continues the SOURCE's seed schedule) come along;
+ *   - the live prefix of the observation rows: n_nodes node rows, n_edges edge rows, n_jobs + 1 entries of dag_ptr, n_jobs of
+ *     exec_supplies (counts: the source's obs_i32 row), the obs_i32 and obs_f64 rows; the copy's next observation relies on the
+ *     edge rows exactly as the source's would;
+ *   - when BOTH stores have timeline arrays, per executor min(count, cap of either) entries and count; else no timeline row is
+ *     read or written.
+ * reseed_dev (nullable, u64[n]): after the copy the destination's generator is numpy's Generator(PCG64(SeedSequence(seed))) afresh.
+ * Job arrivals are all drawn at reset, so such a copy keeps the job sequence and draws its own task durations from there on.
+ * A pair with an id outside its store is skipped. Destination ids must be distinct and, when both stores are the same buffers,
+ * disjoint from the source ids - the caller's duty, the ids live on the device: otherwise an image may be garbage, but nothing
+ * outside the two stores is read or written. Nothing outside the destination images is written. n == 0 does nothing. The launch
+ * is asynchronous on `stream`. (The two structures have no typedef, like sss_timeline's.) */
+struct sss_env_store
+{
+  void* state_dev;            /* u8[num_slots][env_stride] */
+  float* nodes_dev;           /* f32[num_slots][node_cap][3] */
+  int32_t* edge_links_dev;    /* i32[num_slots][edge_cap][2] */
+  int32_t* dag_ptr_dev;       /* i32[num_slots][job_cap + 1] */
+  int32_t* exec_supplies_dev; /* i32[num_slots][job_cap] */
+  int32_t* obs_i32_dev;       /* i32[num_slots][obs_i32] */
+  double* obs_f64_dev;        /* f64[num_slots][obs_f64] */
+  double* tl_t_dev;           /* f64[num_slots][E][tl_cap], or all three NULL: no timeline rows */
+  int32_t* tl_job_dev;        /* i32[num_slots][E][tl_cap] */
+  int32_t* tl_count_dev;      /* i32[num_slots][E] */
+  int32_t tl_cap;
+  int32_t num_slots;
+  uint64_t layout_id;
+};
+struct sss_env_copy_args
+{
+  const struct sss_env_store* src_store; /* NULL: the handle's bound buffers */
+  const struct sss_env_store* dst_store;
+  const int32_t* src_ids_dev;
+  const int32_t* dst_ids_dev;
+  const uint64_t* reseed_dev;
+  int32_t n, pad_;
+};
+uint64_t sss_env_layout_id(const sss_handle* h);
+int sss_env_copy(sss_handle* h, const struct sss_env_copy_args* a, void* stream);
+
 const char* sss_last_error(void);
 void sss_destroy(sss_handle* h);
 

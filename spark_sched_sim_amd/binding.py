@@ -170,6 +170,17 @@ class SssTimelineRenderArgs(C.Structure):  # include/sss.h sss_timeline_render_a
     _fields_ = [("env_ids_dev", C.c_void_p), ("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("pad_", C.c_int32), ("rgb_dev", C.c_void_p)]
 
 
+class SssEnvStore(C.Structure):  # include/sss.h sss_env_store
+    _fields_ = [("state_dev", C.c_void_p), ("nodes_dev", C.c_void_p), ("edge_links_dev", C.c_void_p), ("dag_ptr_dev", C.c_void_p),
+                ("exec_supplies_dev", C.c_void_p), ("obs_i32_dev", C.c_void_p), ("obs_f64_dev", C.c_void_p), ("tl_t_dev", C.c_void_p),
+                ("tl_job_dev", C.c_void_p), ("tl_count_dev", C.c_void_p), ("tl_cap", C.c_int32), ("num_slots", C.c_int32), ("layout_id", C.c_uint64)]
+
+
+class SssEnvCopyArgs(C.Structure):  # include/sss.h sss_env_copy_args
+    _fields_ = [("src_store", C.POINTER(SssEnvStore)), ("dst_store", C.POINTER(SssEnvStore)), ("src_ids_dev", C.c_void_p), ("dst_ids_dev", C.c_void_p),
+                ("reseed_dev", C.c_void_p), ("n", C.c_int32), ("pad_", C.c_int32)]
+
+
 JOB_STATS_COLUMNS = ("num_jobs", "total_job_time", "avg_job_duration", "avg_num_jobs", "avg_completed_job_duration", "num_completed_jobs", "num_active_jobs",
                      "wall_time")  # include/sss.h sss_job_stats: stats[0..7]
 JOB_STATS_MAX_Q = 16
@@ -193,7 +204,7 @@ class SssArenaArgs(C.Structure):  # include/sss.h sss_arena_args
 
 EXPORTS = ["sss_query_dims", "sss_create", "sss_bind_buffers", "sss_reset", "sss_step", "sss_step_bounded", "sss_policy", "sss_rollout",
            "sss_decima_graph_build", "sss_decima_layer_lists", "sss_prefix_rows", "sss_decima_policy", "sss_decima_sample", "sss_gnn_launch",
-           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_bind_timeline", "sss_timeline_render", "sss_decima_argmax", "sss_decima_policy_argmax", "sss_job_stats", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
+           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_bind_timeline", "sss_timeline_render", "sss_decima_argmax", "sss_decima_policy_argmax", "sss_job_stats", "sss_env_layout_id", "sss_env_copy", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
 POLICY_IDS = {"fair": 0, "fifo": 1, "hash": 2, "wfair": 3, "sjfcp": 4}
 WFAIR_ALPHA_RANGE = (-4, 4)  # sss_policy / sss_rollout: the weighted-fair exponent (param of policy 3)
 # the argument structures of include/sss.h and their mirrors here (Binding.check_abi)
@@ -207,6 +218,8 @@ ABI_STRUCTS = {"sss_cfg": SssCfg, "sss_dims": SssDims, "sss_buffers": SssBuffers
 ABI_TAGGED_STRUCTS = {"sss_reward_window_args": SssRewardWindowArgs, "sss_diffret_args": SssDiffretArgs}
 # ... and the ones it declares as `struct name { .. };` alone, without a typedef (tests pin both lists above against lists of their own)
 ABI_PLAIN_STRUCTS = {"sss_timeline": SssTimeline, "sss_timeline_render_args": SssTimelineRenderArgs}
+# ... and the two of sss_env_copy (declared `struct name`, the brace on the next line; tests/fork_util.py pins this list and their fields)
+ABI_STORE_STRUCTS = {"sss_env_store": SssEnvStore, "sss_env_copy_args": SssEnvCopyArgs}
 
 
 def load_library(path: str | None = None) -> C.CDLL:
@@ -260,6 +273,9 @@ class Binding:
         L.sss_decima_argmax.argtypes = [C.c_int, C.c_int, C.POINTER(SssDecimaSampleArgs), C.c_void_p]
         L.sss_decima_policy_argmax.argtypes = [C.c_void_p, C.POINTER(SssDecimaPolicyArgs), C.c_void_p]
         L.sss_job_stats.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        L.sss_env_layout_id.argtypes = [C.c_void_p]
+        L.sss_env_layout_id.restype = C.c_uint64
+        L.sss_env_copy.argtypes = [C.c_void_p, C.POINTER(SssEnvCopyArgs), C.c_void_p]
         L.sss_bit_lists.argtypes = [C.POINTER(SssBitListArgs), C.c_void_p]
         L.sss_arena_append.argtypes = [C.POINTER(SssArenaArgs), C.c_void_p]
         L.sss_rows_op.argtypes = [C.POINTER(SssRowsArgs), C.c_void_p]
@@ -273,7 +289,7 @@ class Binding:
     def check_abi(self) -> None:
         """every ctypes mirror above has the size the library was compiled with (include/sss.h sss_abi_sizeof): a binding and a
         library of different rounds fail here, not inside a kernel"""
-        bad = [(name, C.sizeof(cls), self.lib.sss_abi_sizeof(name.encode())) for name, cls in {**ABI_STRUCTS, **ABI_TAGGED_STRUCTS, **ABI_PLAIN_STRUCTS}.items()
+        bad = [(name, C.sizeof(cls), self.lib.sss_abi_sizeof(name.encode())) for name, cls in {**ABI_STRUCTS, **ABI_TAGGED_STRUCTS, **ABI_PLAIN_STRUCTS, **ABI_STORE_STRUCTS}.items()
                if C.sizeof(cls) != self.lib.sss_abi_sizeof(name.encode())]
         if bad:
             raise RuntimeError("binding / library mismatch (struct, sizeof in binding.py, sizeof in the library): " + ", ".join(map(str, bad)))

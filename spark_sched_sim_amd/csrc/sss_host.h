@@ -19,6 +19,7 @@
 #include "sss_wide.h"
 #include "sss_timeline.h"  // the Gantt rasteriser and its launch (a kernel, or - without a device compiler - plain loops)
 #include "sss_jobstats.h"  // the per-env job statistics and their launch, in the same two forms
+#include "sss_fork.h"      // copies of env images between stores and their launch, in the same two forms
 
 // envs with more than 64 executors run on the wide instantiation of the kernels (sss_wide.h)
 static bool sss_is_wide(int num_executors) { return num_executors > 64; }
@@ -121,6 +122,7 @@ struct sss_handle {
   SssParams P;
   SssPackDev pk;
   SssTimeline tl;  // sss_bind_timeline; t == nullptr: nothing bound
+  uint64_t pack_hash;  // of the workload pack's bytes: part of sss_env_layout_id (job records index the pack)
 };
 
 static int sss_validate(const sss_cfg* cfg, const void* pack, size_t pack_bytes, int num_envs, SssPackHost* ph, int* J_cap) {
@@ -327,8 +329,22 @@ extern "C" int sss_abi_sizeof(const char* name) {
   SSS_ABI_SIZE(sss_gnn_encode_args) SSS_ABI_SIZE(sss_collect_args) SSS_ABI_SIZE(sss_mlp_args) SSS_ABI_SIZE(sss_arena_array)
   SSS_ABI_SIZE(sss_arena_args) SSS_ABI_SIZE(sss_returns_args) SSS_ABI_SIZE(sss_baseline_args) SSS_ABI_SIZE(sss_rows_args) SSS_ABI_SIZE(sss_concat_part) SSS_ABI_SIZE(sss_concat_args) SSS_ABI_SIZE(sss_segcat_args)
   SSS_ABI_SIZE(sss_reward_window_args) SSS_ABI_SIZE(sss_diffret_args) SSS_ABI_SIZE(sss_timeline) SSS_ABI_SIZE(sss_timeline_render_args)
+  SSS_ABI_SIZE(sss_env_store) SSS_ABI_SIZE(sss_env_copy_args)
 #undef SSS_ABI_SIZE
   return -1;
+}
+
+// 64-bit FNV-1a over 8-byte words (and the tail's bytes)
+static uint64_t sss_hash_bytes(const uint8_t* p, size_t n) {
+  uint64_t id = 0xcbf29ce484222325ull;
+  size_t i = 0;
+  for (; i + 8 <= n; i += 8) {
+    uint64_t w;
+    memcpy(&w, p + i, 8);
+    id = (id ^ w) * 0x100000001b3ull;
+  }
+  for (; i < n; i++) id = (id ^ p[i]) * 0x100000001b3ull;
+  return id;
 }
 
 extern "C" int sss_create(const sss_cfg* cfg, const void* pack, size_t pack_bytes, int num_envs, int device, sss_handle** out) {
@@ -341,6 +357,7 @@ extern "C" int sss_create(const sss_cfg* cfg, const void* pack, size_t pack_byte
   sss_handle* h = new sss_handle();
   h->cfg = *cfg, h->ph = ph, h->device = device, h->bound = false;
   h->max_dag_depth = sss_pack_max_depth((const uint8_t*)pack, ph);
+  h->pack_hash = sss_hash_bytes((const uint8_t*)pack, pack_bytes);
   sss_compute_layout(&h->L, num_envs, cfg->num_executors, J_cap, ph.s_max, ph.L, ph.max_edges_per_job, sss_hot_bytes(cfg->num_executors));
   memset(&h->B, 0, sizeof(h->B));
   memset(&h->tl, 0, sizeof(h->tl));
@@ -499,6 +516,69 @@ extern "C" int sss_job_stats(sss_handle* h, int n_q, const double* q_dev, double
   r.n_q = n_q, r.pad_ = 0, r.q = q_dev, r.stats = stats_dev, r.pct = pct_dev, r.sorted = sorted_dev, r.active = active_dev;
   BeDeviceGuard guard(h->device);
   if (int rc = be_launch_job_stats(r, stream)) return sss_fail(-30, std::string("job stats launch failed: ") + be_error(rc));
+  return 0;
+}
+
+// what two envs must share for an image to pass between them: SssLayout without num_envs and state_bytes, the size of the hot
+// region, the instantiation that runs it and the workload pack (job records hold indices into it) - hashed; never 0
+static uint64_t sss_layout_id(const sss_handle* h) {
+  const SssLayout& L = h->L;
+  const int64_t f[] = {L.E, L.J_cap, L.SP, L.L, L.n_pools, L.n_cap, L.ed_cap, L.max_edges_per_job, L.off_active, L.off_jobs, L.off_t_arrival,
+                       L.off_t_completed, L.off_stages, L.off_durations, L.off_pool_hdr, L.off_pool_tab, L.off_dur_ring, L.off_old_active, L.env_stride,
+                       (int64_t)sss_hot_bytes(L.E), (int64_t)sss_is_wide(L.E), (int64_t)sizeof(SssHdr), (int64_t)sss_pool_table_bytes_any(L.E),
+                       (int64_t)h->pack_hash};
+  const uint64_t id = sss_hash_bytes((const uint8_t*)f, sizeof(f));
+  return id ? id : 1;
+}
+extern "C" uint64_t sss_env_layout_id(const sss_handle* h) { return h ? sss_layout_id(h) : 0; }
+
+// a caller's store, checked; `which`: "src_store" / "dst_store"
+static int sss_store_from(const sss_handle* h, const struct sss_env_store* st, const char* which, SssStore* out) {
+  const std::string w = std::string("sss_env_copy: ") + which;
+  if (!st->state_dev || !st->nodes_dev || !st->edge_links_dev || !st->dag_ptr_dev || !st->exec_supplies_dev || !st->obs_i32_dev || !st->obs_f64_dev)
+    return sss_fail(-50, w + ": every state / observation buffer must be provided");
+  if (((uintptr_t)st->state_dev) & 255) return sss_fail(-50, w + ": state_dev must be 256-byte aligned");
+  if (st->num_slots < 1) return sss_fail(-50, w + ": num_slots must be >= 1, got " + std::to_string(st->num_slots));
+  const int n_tl = (st->tl_t_dev != nullptr) + (st->tl_job_dev != nullptr) + (st->tl_count_dev != nullptr);
+  if (n_tl != 0 && n_tl != 3) return sss_fail(-50, w + ": the three timeline arrays come together or not at all");
+  if (n_tl == 3 && st->tl_cap < 1) return sss_fail(-50, w + ": tl_cap must be >= 1, got " + std::to_string(st->tl_cap));
+  if (st->layout_id != sss_layout_id(h))
+    return sss_fail(-51, w + ": the store was made for another env layout (layout id " + std::to_string(st->layout_id) + ", this handle's is " +
+                             std::to_string(sss_layout_id(h)) + "): images pass only between equal layouts");
+  out->state = (uint8_t*)st->state_dev, out->nodes = st->nodes_dev, out->edge_links = st->edge_links_dev, out->dag_ptr = st->dag_ptr_dev;
+  out->exec_supplies = st->exec_supplies_dev, out->obs_i32 = st->obs_i32_dev, out->obs_f64 = st->obs_f64_dev;
+  memset(&out->tl, 0, sizeof(out->tl));
+  if (n_tl == 3) out->tl.t = st->tl_t_dev, out->tl.job = st->tl_job_dev, out->tl.count = st->tl_count_dev, out->tl.cap = st->tl_cap;
+  out->num_slots = st->num_slots, out->gen = SSS_FK_FOREIGN_GEN;
+  return 0;
+}
+static SssStore sss_store_of(const sss_handle* h) {
+  SssStore s;
+  s.state = (uint8_t*)h->B.state, s.nodes = h->B.nodes, s.edge_links = h->B.edge_links, s.dag_ptr = h->B.dag_ptr;
+  s.exec_supplies = h->B.exec_supplies, s.obs_i32 = h->B.obs_i32, s.obs_f64 = h->B.obs_f64;
+  s.tl = h->tl, s.num_slots = h->L.num_envs, s.gen = h->B.gen;
+  return s;
+}
+
+extern "C" int sss_env_copy(sss_handle* h, const struct sss_env_copy_args* a, void* stream) {
+  if (!h || !a) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (a->n < 0) return sss_fail(-50, "sss_env_copy: n must be >= 0, got " + std::to_string(a->n));
+  SssForkArgs r;
+  memset(&r, 0, sizeof(r));
+  r.src = sss_store_of(h), r.dst = r.src;
+  if (a->src_store)
+    if (int rc = sss_store_from(h, a->src_store, "src_store", &r.src)) return rc;
+  if (a->dst_store)
+    if (int rc = sss_store_from(h, a->dst_store, "dst_store", &r.dst)) return rc;
+  if (a->n == 0) return 0;
+  if (!a->src_ids_dev || !a->dst_ids_dev) return sss_fail(-50, "sss_env_copy: src_ids_dev / dst_ids_dev is NULL with n > 0");
+  const SssLayout& L = h->L;
+  r.src_ids = a->src_ids_dev, r.dst_ids = a->dst_ids_dev, r.reseed = a->reseed_dev, r.n = a->n;
+  r.E = L.E, r.J_cap = L.J_cap, r.n_cap = L.n_cap, r.ed_cap = L.ed_cap, r.n_pools = L.n_pools, r.table_bytes = sss_pool_table_bytes_any(L.E);
+  r.env_stride = L.env_stride, r.off_pool_hdr = L.off_pool_hdr, r.off_pool_tab = L.off_pool_tab, r.off_dur_ring = L.off_dur_ring;
+  BeDeviceGuard guard(h->device);
+  if (int rc = be_launch_env_copy(r, stream)) return sss_fail(-30, std::string("env copy launch failed: ") + be_error(rc));
   return 0;
 }
 

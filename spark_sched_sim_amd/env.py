@@ -52,9 +52,9 @@ class SparkSchedSimEnv(_Base):  # type: ignore[misc]
     RENDER_SIZE = (400, 300)  # width, height of an "rgb_array" frame
     TIMELINE_CAP = 512        # history entries kept per executor (whole episodes of the usual configurations need ~100)
 
-    def __init__(self, env_cfg: dict[str, Any], device: str = "cuda:0", _lib=None, record_history: bool = True) -> None:
+    def __init__(self, env_cfg: dict[str, Any], device: str = "cuda:0", _lib=None, record_history: bool = True, pack: bytes | None = None) -> None:
         """`record_history=False` (not with a render mode): `Executor.history` is not kept - the env then runs the kernels
-        without recording and allocates no timeline rows; `executors[i].history` raises"""
+        without recording and allocates no timeline rows; `executors[i].history` raises. `pack`: a workload pack other than the default"""
         render_mode = env_cfg.get("render_mode")
         if render_mode and render_mode != "rgb_array":
             raise ValueError("rendering is not available in the GPU build")  # the pygame window ("human") is out of scope
@@ -66,7 +66,8 @@ class SparkSchedSimEnv(_Base):  # type: ignore[misc]
         from .spaces import make_action_space, make_observation_space
         self.action_space = make_action_space(self.num_executors)
         self.observation_space = make_observation_space(self.num_executors)
-        self._vec = VecSparkSchedSimEnv({k: v for k, v in env_cfg.items() if k != "render_mode"}, 1, device=device, _lib=_lib)
+        self._vec = VecSparkSchedSimEnv({k: v for k, v in env_cfg.items() if k != "render_mode"}, 1, device=device, _lib=_lib, pack=pack)
+        self._ctor = (dict(env_cfg), _lib, bool(record_history))  # what __deepcopy__ builds the copy from
         if render_mode and not record_history:
             raise ValueError("render_mode needs record_history=True")
         if record_history:  # Executor.history is kept unless the caller opts out, as in the reference
@@ -103,6 +104,20 @@ class SparkSchedSimEnv(_Base):  # type: ignore[misc]
         o = self._vec.obs_i32[0].cpu().numpy()
         reward = self._vec.obs_f64[0, 0].item()
         return self._observe(), reward, bool(o[6]), False, self.info
+
+    def __deepcopy__(self, memo) -> "SparkSchedSimEnv":
+        """the reference's `copy.deepcopy(env)`, also in the middle of an episode: a new env of the same configuration, workload
+        pack and device that holds this env's image (VecSparkSchedSimEnv.snapshot / restore: state, observation, executor
+        histories) and the Python-side fields this facade keeps current. The two step independently from here on."""
+        env_cfg, lib, record_history = self._ctor
+        new = type(self)(env_cfg, device=str(self._vec.device), _lib=lib, record_history=record_history, pack=self._vec._pack)
+        new._vec.restore(self._vec.snapshot([0]), [0])
+        new.job_arrival_cap, new.render_mode = self.job_arrival_cap, self.render_mode
+        new.observation_space["source_job_idx"].n = self.observation_space["source_job_idx"].n
+        new.action_space["stage_idx"].n = self.action_space["stage_idx"].n
+        new.observation_space["dag_ptr"].feature_space.n = self.observation_space["dag_ptr"].feature_space.n
+        memo[id(self)] = new
+        return new
 
     def _observe(self) -> dict:
         obs = self._vec.obs_view(0)

@@ -65,6 +65,47 @@ def run_episodes(env, actor, seed, max_steps: int = 200_000, *, param: int = 0, 
     return _summarize(env, q)
 
 
+@torch.no_grad()
+def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_steps: int = 200_000, *, q: Sequence[float] = (25, 50, 75, 100),
+                  check_every: int = DECISION_CHECK_EVERY) -> dict[str, torch.Tensor]:
+    """the cost-to-go of env states under an on-device policy: `env.fork(src, dst, reseed)` - `reseed` gives every child its own
+    task-duration noise on the parent's job sequence - then ONLY the `dst` envs play to the end of their episodes under `policy` /
+    `param` (`VecSparkSchedSimEnv.policy_actions`); every other env sits the launches out (SSS_SKIP_ENV) and keeps its state,
+    outputs and counters byte for byte. `src` / `dst`: host-side ids (their number sizes the result). Returns the `run_episodes`
+    dict with one row per child, in the order of `dst` (`ok`: the child's episode ended without an env error); the done mask is read
+    every `check_every` steps, at most `max_steps` steps are played."""
+    from .training import SKIP_ENV
+
+    if env.auto_reset:
+        raise ValueError("continuations: the env must not auto-reset (a finished child's statistics are read from its arena block)")
+    B, dev = env.num_envs, env.device
+    dst_l = [int(dst)] if isinstance(dst, int) else [int(x) for x in dst]
+    env.fork(src, dst_l, reseed=reseed)
+    idx = torch.tensor(dst_l, dtype=torch.long).to(dev)
+    child = torch.zeros(B, dtype=torch.bool, device=dev)
+    child[idx] = True
+    skip = torch.full((B,), SKIP_ENV, dtype=torch.int32, device=dev)
+    done = ~child
+    t = 0
+    while t < max_steps:
+        for _ in range(min(int(check_every), max_steps - t)):
+            done = done | (env.obs_i32[:, 6] != 0) | (env.obs_i32[:, 7] != 0)
+            act = env.policy_actions(policy, param)
+            env.step_async(torch.where(done, skip, act["stage_idx"]).contiguous(), act["num_exec"])
+            t += 1
+        if bool((done | (env.obs_i32[:, 6] != 0) | (env.obs_i32[:, 7] != 0)).all()):
+            break
+    r = env.job_stats(q, active=child, want_sorted=True)
+    out = {name: r["stats"][idx, k].clone() for k, name in enumerate(JOB_STATS_COLUMNS)}
+    out["avg_job_duration_s"] = out["avg_completed_job_duration"]
+    out["episode_avg_job_duration_s"] = out["avg_job_duration"] * 1e-3
+    out["pct"], out["sorted"] = r["pct"][idx].clone(), r["sorted"][idx].clone()
+    out["q"] = torch.tensor([float(x) for x in q], dtype=torch.float64)
+    out["ok"] = ((env.header_field("terminated") != 0) & (env.obs_i32[:, 7] == 0))[idx].clone()
+    out["steps"] = env.header_field("ep_steps")[idx].clone()
+    return out
+
+
 def _ci95(v: torch.Tensor, n: int) -> float:
     return float(1.96 * v.std() / n ** 0.5)
 

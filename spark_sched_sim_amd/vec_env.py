@@ -683,6 +683,170 @@ class VecSparkSchedSimEnv:
             tot[name + "_events" if name != "n_rounds" else name] = int(np.ascontiguousarray(hdr[:, off: off + 8]).view(np.uint64).sum())
         return tot
 
+    # ---- copies of running envs: fork, snapshot, restore (include/sss.h sss_env_copy) -----------
+
+    @property
+    def layout_id(self) -> int:
+        """what two envs must share for an image to pass between them (include/sss.h sss_env_layout_id): every capacity and offset
+        of an env's block and the kernel instantiation - not num_envs"""
+        return int(self._b.lib.sss_env_layout_id(self._h))
+
+    def _copy_ids(self, ids, what: str, limit: int) -> tuple[torch.Tensor, list[int] | None]:
+        """ids for sss_env_copy as (i32 tensor on the device, the host's list or None). An int or a host sequence is checked against
+        [0, limit); a tensor is passed through as it is - its values stay on the device, the kernel skips ids outside the store"""
+        if isinstance(ids, torch.Tensor):
+            return ids.reshape(-1).to(device=self.device, dtype=torch.int32).contiguous(), None
+        host = [int(ids)] if isinstance(ids, (int, np.integer)) else [int(x) for x in ids]
+        bad = [x for x in host if not 0 <= x < limit]
+        if bad:
+            raise ValueError(f"{what}: id {bad[0]} is outside [0, {limit})")
+        return torch.tensor(host, dtype=torch.int32).to(self.device), host
+
+    @staticmethod
+    def _check_pairs(src: list[int] | None, dst: list[int] | None, same_store: bool, what: str) -> None:
+        if dst is not None and len(set(dst)) != len(dst):
+            raise ValueError(f"{what}: destination ids must be distinct, got {dst}")
+        if same_store and src is not None and dst is not None and set(src) & set(dst):
+            raise ValueError(f"{what}: destination ids {sorted(set(src) & set(dst))} are also source ids")
+
+    def _own_store(self):
+        """this env's buffers as an sss_env_store (for a call on ANOTHER handle; on its own handle a NULL store says the same)"""
+        from .binding import SssEnvStore
+        tl = getattr(self, "_timeline", None)
+        t, job, count = tl if tl is not None else (None, None, None)
+        return SssEnvStore(self.state.data_ptr(), self.nodes.data_ptr(), self.edge_links.data_ptr(), self.dag_ptr.data_ptr(), self.exec_supplies.data_ptr(),
+                           self.obs_i32.data_ptr(), self.obs_f64.data_ptr(), t.data_ptr() if tl else None, job.data_ptr() if tl else None,
+                           count.data_ptr() if tl else None, t.shape[2] if tl else 0, self.num_envs, self.layout_id)
+
+    def _env_copy(self, src_store, dst_store, src_ids: torch.Tensor, dst_ids: torch.Tensor, reseed: torch.Tensor | None) -> None:
+        from .binding import SssEnvCopyArgs
+        n = int(src_ids.numel())
+        if int(dst_ids.numel()) != n or (reseed is not None and int(reseed.numel()) != n):
+            raise ValueError(f"env copy: {n} source ids, {int(dst_ids.numel())} destination ids" + (f", {int(reseed.numel())} seeds" if reseed is not None else ""))
+        a = SssEnvCopyArgs(C.pointer(src_store) if src_store is not None else None, C.pointer(dst_store) if dst_store is not None else None,
+                           src_ids.data_ptr() if n else None, dst_ids.data_ptr() if n else None, reseed.data_ptr() if reseed is not None and n else None, n, 0)
+        self._b.check(self._b.lib.sss_env_copy(self._h, C.byref(a), self._stream()))
+
+    def _seed_tensor(self, reseed, n: int) -> torch.Tensor | None:
+        """seeds in [0, 2^64) as the u64[n] array the kernel reads (an int64 tensor holding the same bits)"""
+        if reseed is None:
+            return None
+        if isinstance(reseed, torch.Tensor):
+            return reseed.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        vals = [int(reseed)] * n if isinstance(reseed, (int, np.integer)) else [int(x) for x in reseed]
+        if any(not 0 <= v < 2 ** 64 for v in vals):
+            raise ValueError("reseed: seeds must be in [0, 2**64)")
+        return torch.from_numpy(np.asarray(vals, dtype=np.uint64).view(np.int64).copy()).to(self.device)
+
+    def _mirrors(self):
+        """the per-env arrays kept beside the arena: reset seeds, time limits, the bounded-step `ready` flags (None until first used)"""
+        return (self._seeds, self._tl, getattr(self, "_ready", None))
+
+    @staticmethod
+    def _copy_mirrors(src, n_src: int, src_ids: torch.Tensor, dst, n_dst: int, dst_ids: torch.Tensor) -> None:
+        """dst[k][dst_ids] = src[k][src_ids] for the pairs the kernel takes - both ids inside their stores - with device ops only
+        (the ids may live on the device: a pair the kernel skips goes to a spare element instead of an index out of range)"""
+        if not int(src_ids.numel()):
+            return
+        s, d = src_ids.long(), dst_ids.long()
+        valid = (s >= 0) & (s < n_src) & (d >= 0) & (d < n_dst)
+        s, d = s.clamp(0, n_src - 1), torch.where(valid, d, torch.full_like(d, n_dst))
+        for a, b in zip(src, dst):
+            if a is None or b is None:
+                continue
+            ext = torch.cat([b[:n_dst], b.new_zeros(1)])
+            ext[d] = a.to(b.device)[s]
+            b[:n_dst].copy_(ext[:n_dst])
+
+    def fork(self, src, dst, reseed=None) -> None:
+        """env dst[k] becomes a copy of env src[k] - the reference's `copy.deepcopy(env)` (everything spark_sched_sim.py:34-125 sets up,
+        in whatever state the episode has brought it to, a step cut by `step_bounded_async` included) for every pair in one launch,
+        asynchronous on the current stream. The copy continues exactly as the source would; with `reseed` (an int for all, or one
+        per pair; numpy's `default_rng(seed)`) it keeps the job sequence - every arrival is drawn at reset - and draws its own task
+        durations from there on. The destination keeps its own lifetime counters (`counters()` is unchanged), its observation rows
+        and - when a timeline is recorded - its timeline rows become the source's.
+        `src`, `dst`: an int, a sequence or a tensor of env ids. Host-side ids are checked - in range, `dst` distinct and disjoint from
+        `src` (ValueError, nothing is written) - tensors are passed to the kernel without a sync: the rule is then the caller's duty,
+        ids out of range are skipped. A copy's next episode under auto-reset follows the SOURCE's seed schedule (the episode's seed
+        is part of the image)."""
+        s_t, s_h = self._copy_ids(src, "fork: src", self.num_envs)
+        d_t, d_h = self._copy_ids(dst, "fork: dst", self.num_envs)
+        self._check_pairs(s_h, d_h, True, "fork")
+        seeds = self._seed_tensor(reseed, int(s_t.numel()))
+        self._env_copy(None, None, s_t, d_t, seeds)
+        self._copy_mirrors(self._mirrors(), self.num_envs, s_t, self._mirrors(), self.num_envs, d_t)
+
+    def snapshot(self, env_ids=None) -> "EnvSnapshot":
+        """the images of `env_ids` (default: all envs) in tensors of their own: slot k holds env_ids[k] as it is now (asynchronous).
+        `restore` brings them back - into this env or another one of the same layout."""
+        ids, host = self._copy_ids(range(self.num_envs) if env_ids is None else env_ids, "snapshot: env_ids", self.num_envs)
+        snap = EnvSnapshot(self, int(ids.numel()))
+        slots = torch.arange(snap.num_slots, dtype=torch.int32, device=self.device)
+        self._env_copy(None, snap._store(), ids, slots, None)
+        self._copy_mirrors(self._mirrors(), self.num_envs, ids, (snap.seeds, snap.time_limits, snap.ready), snap.num_slots, slots)
+        snap.env_ids = host
+        return snap
+
+    def restore(self, snap: "EnvSnapshot", env_ids=None, slots=None) -> None:
+        """env env_ids[k] becomes the image in slot slots[k] of `snap` (defaults: every slot, into the envs it was taken from - or
+        0 .. m - 1 when those are not known on the host). `snap` may come from another `VecSparkSchedSimEnv` of the same layout
+        (`layout_id`: same env_cfg capacities and workload pack, any num_envs); another layout raises ValueError. Lifetime counters stay
+        the env's own, as for `fork`. Timeline rows move only when the snapshot holds them AND this env records a timeline: a
+        snapshot without them leaves this env's rows untouched (they then describe the env's previous state), and an env without
+        a timeline ignores the snapshot's."""
+        if snap.layout_id != self.layout_id:
+            raise ValueError(f"restore: the snapshot was taken from another env layout (layout id {snap.layout_id}, this env's is {self.layout_id}); "
+                             "images pass only between envs of the same capacities, workload pack and executor-count class")
+        sl_t, sl_h = self._copy_ids(range(snap.num_slots) if slots is None else slots, "restore: slots", snap.num_slots)
+        if env_ids is None:
+            env_ids = [snap.env_ids[k] for k in sl_h] if snap.env_ids is not None and sl_h is not None and max(snap.env_ids, default=-1) < self.num_envs else range(int(sl_t.numel()))
+        e_t, e_h = self._copy_ids(env_ids, "restore: env_ids", self.num_envs)
+        self._check_pairs(None, e_h, False, "restore")
+        self._env_copy(snap._store(), None, sl_t, e_t, None)
+        self._copy_mirrors((snap.seeds, snap.time_limits, snap.ready), snap.num_slots, sl_t, self._mirrors(), self.num_envs, e_t)
+
+
+class EnvSnapshot:
+    """`num_slots` env images (`VecSparkSchedSimEnv.snapshot`) in tensors laid out as a store of include/sss.h sss_env_copy: blocks of
+    a state arena, rows of the six observation buffers and - when the env recorded a timeline - of the three timeline arrays, plus the
+    host-side mirrors of the envs (`seeds`, `time_limits`, the bounded-step `ready` flags) and the `layout_id` they belong to."""
+
+    def __init__(self, env: VecSparkSchedSimEnv, m: int) -> None:
+        d, dev, n = env.dims, env.device, max(int(m), 1)  # (at least one slot is allocated: no NULL pointers)
+        self.num_slots, self.layout_id, self.device = int(m), env.layout_id, dev
+        self._state_raw = torch.zeros(n * d.env_stride + 256, dtype=torch.uint8, device=dev)
+        off = (-self._state_raw.data_ptr()) % 256
+        self.state = self._state_raw[off: off + n * d.env_stride]
+        self.nodes = torch.zeros((n, d.node_cap, NUM_NODE_FEATURES), dtype=torch.float32, device=dev)
+        self.edge_links = torch.zeros((n, d.edge_cap, 2), dtype=torch.int32, device=dev)
+        self.dag_ptr = torch.zeros((n, d.job_cap + 1), dtype=torch.int32, device=dev)
+        self.exec_supplies = torch.zeros((n, d.job_cap), dtype=torch.int32, device=dev)
+        self.obs_i32 = torch.zeros((n, d.obs_i32), dtype=torch.int32, device=dev)
+        self.obs_f64 = torch.zeros((n, d.obs_f64), dtype=torch.float64, device=dev)
+        self.timeline = None
+        tl = getattr(env, "_timeline", None)
+        if tl is not None:
+            E, cap = env.num_executors, tl[0].shape[2]
+            self.timeline = (torch.full((n, E, cap), float("nan"), dtype=torch.float64, device=dev), torch.full((n, E, cap), -1, dtype=torch.int32, device=dev),
+                             torch.ones((n, E), dtype=torch.int32, device=dev))
+        self.seeds = torch.zeros(n, dtype=torch.int64, device=dev)[: self.num_slots]
+        self.time_limits = torch.full((n,), float("inf"), dtype=torch.float64, device=dev)[: self.num_slots]
+        self.ready = torch.ones(n, dtype=torch.uint8, device=dev)[: self.num_slots]
+        self.env_ids: list[int] | None = None
+
+    def _store(self):
+        from .binding import SssEnvStore
+        tl = self.timeline
+        return SssEnvStore(self.state.data_ptr(), self.nodes.data_ptr(), self.edge_links.data_ptr(), self.dag_ptr.data_ptr(), self.exec_supplies.data_ptr(),
+                           self.obs_i32.data_ptr(), self.obs_f64.data_ptr(), tl[0].data_ptr() if tl else None, tl[1].data_ptr() if tl else None,
+                           tl[2].data_ptr() if tl else None, tl[0].shape[2] if tl else 0, max(self.num_slots, 1), self.layout_id)
+
+    @property
+    def nbytes(self) -> int:
+        """bytes of device memory the snapshot's tensors hold"""
+        ts = [self._state_raw, self.nodes, self.edge_links, self.dag_ptr, self.exec_supplies, self.obs_i32, self.obs_f64, *(self.timeline or ())]
+        return int(sum(t.numel() * t.element_size() for t in ts))
+
 
 # byte offset of SssHot::ex_job (i16 per executor) inside an env's arena block, by the kernels' executor capacity (csrc/sss_layout.h:
 # 64 up to 64 executors, 128 in the wide instantiation); pinned by tests/test_emu_timeline.py against the header compiled with g++

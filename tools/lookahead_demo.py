@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""Lookahead from one state: an env plays `--at` steps of one job sequence under the fair scheduler; from THAT state every candidate
+scheduler gets `--samples` forked children (`evaluation.continuations`: same job sequence, each child its own task-duration noise)
+which play to the end of the episode on the device. Prints each scheduler's cost-to-go - the episode's mean job duration and the
+time-average number of jobs in the system - with a 95 % confidence interval over the samples.
+
+    python tools/lookahead_demo.py [--seed 0] [--at 150] [--samples 64] [--policies fair,fifo,sjfcp,wfair:1]
+"""
+from __future__ import annotations
+
+import argparse
+import os.path as osp
+import sys
+
+import torch
+
+ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from spark_sched_sim_amd import VecSparkSchedSimEnv, evaluation  # noqa: E402
+
+C1 = dict(num_executors=10, job_arrival_cap=50, job_arrival_rate=4.0e-5, moving_delay=2000.0, warmup_delay=1000.0)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--at", type=int, default=150, help="steps the parent plays before the fork")
+    ap.add_argument("--samples", type=int, default=64)
+    ap.add_argument("--policies", default="fair,fifo,sjfcp,wfair:1", help="on-device policies, name[:param]")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args()
+    policies = [(p.split(":")[0], int(p.split(":")[1]) if ":" in p else 0) for p in args.policies.split(",")]
+    S = args.samples
+    env = VecSparkSchedSimEnv(C1, 1 + S, device=args.device)
+    env.reset(seed=[args.seed] * (1 + S))
+    skip = torch.full((1 + S,), -2147483648, dtype=torch.int32, device=env.device)
+    for _ in range(args.at):  # the parent alone
+        a = env.policy_actions("fair")
+        skip[0] = a["stage_idx"][0]
+        env.step_async(skip, a["num_exec"])
+    h = env.header(0)
+    print(f"state: seed {args.seed} after {args.at} steps of 'fair': wall_time {h['wall_time']:.0f} ms, {h['n_active']} jobs active, {h['n_completed']} of {h['J']} completed")
+    children = list(range(1, 1 + S))
+    for name, param in policies:
+        r = evaluation.continuations(env, [0] * S, children, name, param=param, reseed=[1000 + k for k in range(S)])
+        ok = r["ok"]
+        n = int(ok.sum())
+        dur, jobs = r["episode_avg_job_duration_s"][ok], r["avg_num_jobs"][ok]
+        ci = lambda v: float(1.96 * v.std() / max(n, 1) ** 0.5) if n > 1 else float("nan")  # noqa: E731
+        print(f"{name + (':' + str(param) if param else ''):10s} mean job duration {float(dur.mean()):8.2f} +- {ci(dur):.2f} s   avg jobs in system {float(jobs.mean()):6.2f} +- {ci(jobs):.2f}   "
+              f"({n} of {S} children finished)")
+    env.close()
+
+
+if __name__ == "__main__":
+    main()
