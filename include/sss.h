@@ -874,6 +874,55 @@ struct sss_env_copy_args
 uint64_t sss_env_layout_id(const sss_handle* h);
 int sss_env_copy(sss_handle* h, const struct sss_env_copy_args* a, void* stream);
 
+/* The fused rollout with a policy PER ENV: sss_rollout for the envs that take part, each under its own on-device policy, the others
+ * untouched - what a lookahead needs of the fused kernel (children of one state under different policies in one launch while their
+ * parents sit still; the reference has no counterpart: its schedulers are host objects, one env per process). Every array is per
+ * env of the handle, i32[num_envs]:
+ *   policy_dev        the policy id of the env's steps, the ids of sss_policy. -1: env i is left completely untouched - state,
+ *                     observation rows, outputs and counters stay byte for byte, as under SSS_SKIP_ENV in sss_step - and none of
+ *                     the outputs below is written for it
+ *   param_dev         that policy's param
+ *   first_policy_dev, first_param_dev   (both NULL, or both given) the policy and param of the env's FIRST step in this launch; a
+ *                     negative first_policy entry, like NULL, means policy_dev / param_dev. "Child k plays candidate k throughout"
+ *                     and "child k takes candidate k's action, then the base policy" are the same call
+ *   n_steps           upper bound of steps per env, >= 0. There is NO auto-reset: an env stops at the end of its episode or at an
+ *                     env error (as sss_rollout does with auto_reset == 0); an env that is over at entry takes no step and no byte
+ *                     of it is written
+ *   steps_dev         (nullable) out: steps the env took in this launch
+ *   first_stage_dev, first_exec_dev   (nullable) out: the action (stage_idx, num_exec) of the first step taken; left alone when
+ *                     the env took none
+ * Per-step semantics are exactly those of sss_policy + sss_step, bit for bit; only the last observation survives.
+ * The arrays live on the device and no sync is spent on reading them, so their CONTENTS are the caller's duty: for a policy id
+ * outside the table (other than -1) or a weighted-fair alpha outside [-4, 4] - in either pair - the kernel leaves env i untouched and
+ * reports steps_dev[i] = -1. Refused on the host with -52, before any launch: NULL policy_dev or param_dev, one of the first_* pair
+ * without the other, n_steps < 0, and a bound timeline ("not available while a timeline is recorded": this kernel has no recording
+ * form - unbind, or use sss_policy + sss_step). */
+int sss_rollout_each(sss_handle* h, const int32_t* policy_dev, const int32_t* param_dev, const int32_t* first_policy_dev, const int32_t* first_param_dev,
+                     int n_steps, int32_t* steps_dev, int32_t* first_stage_dev, int32_t* first_exec_dev, void* stream);
+
+/* From the children of a lookahead to its decision, in one launch (one wavefront per parent; the arena is only read). Parent i
+ * (parent_dev i32[n_parents], env ids) has n_candidates x n_samples children, child_dev i32[n_parents][n_candidates][n_samples]: env
+ * ids of copies of the parent (sss_env_copy) that were played to the end of their episodes, candidate k's under the policies
+ * cand_first_policy_dev[k], cand_first_param_dev[k] (first step) and cand_policy_dev[k], cand_param_dev[k] (after it), i32[n_candidates]
+ * each - the kernel does not interpret these four, it hands them on.
+ *   cost of a child   stats[1] of sss_job_stats for that env, the same bits: ((0.0 + d_0) + d_1) + ... with
+ *                     d_j = min(t_completed[j], wall_time) - t_arrival[j] over the arrived jobs in job-id order
+ *   a child is valid  when its episode is over without an env error (terminated != 0 and err == 0). Only then are the costs of two
+ *                     children comparable: they cover the same jobs from arrival to completion. An id outside [0, num_envs) is invalid
+ *   score of k        ((0.0 + cost[k][0]) + cost[k][1]) + ... in sample order, then ONE division by n_samples; NaN when any of k's
+ *                     samples is invalid
+ *   winner            the lowest score; ties go to the lowest k; a NaN never wins
+ * Outputs: best_dev i32[n_parents] the winner, -1 when no candidate is valid; score_dev f64[n_parents][n_candidates]; and the
+ * winner's quadruple - candidate 0's when there is no winner - written to env_first_policy_dev, env_first_param_dev, env_policy_dev,
+ * env_param_dev (i32[num_envs] each) at index parent_dev[i]: arrays that are -1 elsewhere are the arguments of the sss_rollout_each
+ * launch that steps the parents by the decision. A parent id outside [0, num_envs) gets its best / score rows and nothing else.
+ * n_candidates, n_samples >= 1, n_candidates * n_samples <= 1024 (the kernel's LDS cost table), n_parents >= 0 (0 does nothing);
+ * anything else, or a NULL array, fails with -53. (Plain parameters, like sss_job_stats.) */
+int sss_lookahead_pick(sss_handle* h, int n_parents, int n_candidates, int n_samples, const int32_t* parent_dev, const int32_t* child_dev,
+                       const int32_t* cand_first_policy_dev, const int32_t* cand_first_param_dev, const int32_t* cand_policy_dev,
+                       const int32_t* cand_param_dev, int32_t* best_dev, double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev,
+                       int32_t* env_policy_dev, int32_t* env_param_dev, void* stream);
+
 const char* sss_last_error(void);
 void sss_destroy(sss_handle* h);
 

@@ -20,6 +20,7 @@
 #include "sss_timeline.h"  // the Gantt rasteriser and its launch (a kernel, or - without a device compiler - plain loops)
 #include "sss_jobstats.h"  // the per-env job statistics and their launch, in the same two forms
 #include "sss_fork.h"      // copies of env images between stores and their launch, in the same two forms
+#include "sss_lookahead.h" // the winner among a lookahead's children and its launch, in the same two forms
 
 // envs with more than 64 executors run on the wide instantiation of the kernels (sss_wide.h)
 static bool sss_is_wide(int num_executors) { return num_executors > 64; }
@@ -642,6 +643,53 @@ extern "C" int sss_rollout(sss_handle* h, int policy, int param, int n_steps, in
   const SssKernelArgs ka = sss_args(h);
   if (int rc = sss_is_wide(h->L.E) ? sss_wide_launch_rollout(ka, h->L.num_envs, policy, param, n_steps, auto_reset, seed_stride, stream)
                                    : be_launch_rollout(ka, h->L.num_envs, policy, param, n_steps, auto_reset, seed_stride, stream)) return sss_fail(-30, std::string("rollout launch failed: ") + be_error(rc));
+  return 0;
+}
+
+extern "C" int sss_rollout_each(sss_handle* h, const int32_t* policy_dev, const int32_t* param_dev, const int32_t* first_policy_dev, const int32_t* first_param_dev,
+                                int n_steps, int32_t* steps_dev, int32_t* first_stage_dev, int32_t* first_exec_dev, void* stream) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (!policy_dev) return sss_fail(-52, "sss_rollout_each: policy_dev is NULL");
+  if (!param_dev) return sss_fail(-52, "sss_rollout_each: param_dev is NULL");
+  if ((first_policy_dev != nullptr) != (first_param_dev != nullptr)) return sss_fail(-52, "sss_rollout_each: first_policy_dev and first_param_dev come together or not at all");
+  if (n_steps < 0) return sss_fail(-52, "sss_rollout_each: n_steps must be >= 0, got " + std::to_string(n_steps));
+  if (h->tl.t) return sss_fail(-52, "sss_rollout_each: not available while a timeline is recorded (sss_bind_timeline; this kernel has no recording form)");
+  BeDeviceGuard guard(h->device);
+  const SssKernelArgs ka = sss_args(h);
+  if (int rc = sss_is_wide(h->L.E) ? sss_wide_launch_rollout_each(ka, h->L.num_envs, policy_dev, param_dev, first_policy_dev, first_param_dev, n_steps, steps_dev,
+                                                                  first_stage_dev, first_exec_dev, stream)
+                                   : sss_narrow_launch_rollout_each(ka, h->L.num_envs, policy_dev, param_dev, first_policy_dev, first_param_dev, n_steps, steps_dev,
+                                                                    first_stage_dev, first_exec_dev, stream))
+    return sss_fail(-30, std::string("rollout launch failed: ") + be_error(rc));
+  return 0;
+}
+
+extern "C" int sss_lookahead_pick(sss_handle* h, int n_parents, int n_candidates, int n_samples, const int32_t* parent_dev, const int32_t* child_dev,
+                                  const int32_t* cand_first_policy_dev, const int32_t* cand_first_param_dev, const int32_t* cand_policy_dev,
+                                  const int32_t* cand_param_dev, int32_t* best_dev, double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev,
+                                  int32_t* env_policy_dev, int32_t* env_param_dev, void* stream) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (n_parents < 0) return sss_fail(-53, "sss_lookahead_pick: n_parents must be >= 0, got " + std::to_string(n_parents));
+  if (n_candidates < 1 || n_samples < 1 || (int64_t)n_candidates * n_samples > SSS_LA_MAX_CHILDREN)
+    return sss_fail(-53, "sss_lookahead_pick: candidates and samples must be >= 1 and their product at most " + std::to_string(SSS_LA_MAX_CHILDREN) + ", got " +
+                             std::to_string(n_candidates) + " x " + std::to_string(n_samples));
+  if (n_parents == 0) return 0;
+  if (!parent_dev || !child_dev) return sss_fail(-53, "sss_lookahead_pick: parent_dev / child_dev is NULL");
+  if (!cand_first_policy_dev || !cand_first_param_dev || !cand_policy_dev || !cand_param_dev) return sss_fail(-53, "sss_lookahead_pick: a candidate array is NULL");
+  if (!best_dev || !score_dev) return sss_fail(-53, "sss_lookahead_pick: best_dev / score_dev is NULL");
+  if (!env_first_policy_dev || !env_first_param_dev || !env_policy_dev || !env_param_dev) return sss_fail(-53, "sss_lookahead_pick: a per-env policy array is NULL");
+  SssLookaheadArgs r;
+  memset(&r, 0, sizeof(r));
+  r.js.state = (const uint8_t*)h->B.state, r.js.env_stride = h->L.env_stride, r.js.off_t_arrival = h->L.off_t_arrival, r.js.off_t_completed = h->L.off_t_completed;
+  r.js.off_dur_ring = h->L.off_dur_ring, r.js.num_envs = h->L.num_envs, r.js.J_cap = h->L.J_cap;
+  r.n_parents = n_parents, r.K = n_candidates, r.S = n_samples, r.parent = parent_dev, r.child = child_dev;
+  r.cand_first_policy = cand_first_policy_dev, r.cand_first_param = cand_first_param_dev, r.cand_policy = cand_policy_dev, r.cand_param = cand_param_dev;
+  r.best = best_dev, r.score = score_dev;
+  r.env_first_policy = env_first_policy_dev, r.env_first_param = env_first_param_dev, r.env_policy = env_policy_dev, r.env_param = env_param_dev;
+  BeDeviceGuard guard(h->device);
+  if (int rc = be_launch_lookahead_pick(r, stream)) return sss_fail(-30, std::string("lookahead pick launch failed: ") + be_error(rc));
   return 0;
 }
 

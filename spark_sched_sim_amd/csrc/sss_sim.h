@@ -787,6 +787,8 @@ SSS_KERNEL void SSS_KNAME(sss_rollout_heur_kernel)(SssKernelArgs a, int policy, 
 #undef ROLLOUT_BODY
 #undef SSS_ROLLOUT_HEURISTICS
 
+#include "sss_sim_each.h"  // the fused rollout with a policy per env (sss_rollout_each): a kernel of its own, and the emulator's launchers of it
+
 #undef H
 #undef FAIL
 #undef CHECK

@@ -67,13 +67,16 @@ def run_episodes(env, actor, seed, max_steps: int = 200_000, *, param: int = 0, 
 
 @torch.no_grad()
 def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_steps: int = 200_000, *, q: Sequence[float] = (25, 50, 75, 100),
-                  check_every: int = DECISION_CHECK_EVERY) -> dict[str, torch.Tensor]:
+                  check_every: int = DECISION_CHECK_EVERY, fused: bool = False) -> dict[str, torch.Tensor]:
     """the cost-to-go of env states under an on-device policy: `env.fork(src, dst, reseed)` - `reseed` gives every child its own
     task-duration noise on the parent's job sequence - then ONLY the `dst` envs play to the end of their episodes under `policy` /
     `param` (`VecSparkSchedSimEnv.policy_actions`); every other env sits the launches out (SSS_SKIP_ENV) and keeps its state,
     outputs and counters byte for byte. `src` / `dst`: host-side ids (their number sizes the result). Returns the `run_episodes`
     dict with one row per child, in the order of `dst` (`ok`: the child's episode ended without an env error); the done mask is read
-    every `check_every` steps, at most `max_steps` steps are played."""
+    every `check_every` steps, at most `max_steps` steps are played.
+    `fused=True`: the children play in ONE launch of the fused rollout with a policy per env (`env.rollout_each`) instead of a policy
+    and a step launch per step of the longest child - the same results, bit for bit, and no done mask to read; not available while
+    the env records a timeline."""
     from .training import SKIP_ENV
 
     if env.auto_reset:
@@ -87,6 +90,11 @@ def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_s
     skip = torch.full((B,), SKIP_ENV, dtype=torch.int32, device=dev)
     done = ~child
     t = 0
+    if fused:
+        pid = env._policy_id(policy, param)
+        sit_out = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        env.rollout_each(torch.where(child, torch.full_like(sit_out, pid), sit_out), torch.where(child, torch.full_like(sit_out, int(param)), sit_out), int(max_steps))
+        t = max_steps
     while t < max_steps:
         for _ in range(min(int(check_every), max_steps - t)):
             done = done | (env.obs_i32[:, 6] != 0) | (env.obs_i32[:, 7] != 0)
@@ -103,6 +111,53 @@ def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_s
     out["q"] = torch.tensor([float(x) for x in q], dtype=torch.float64)
     out["ok"] = ((env.header_field("terminated") != 0) & (env.obs_i32[:, 7] == 0))[idx].clone()
     out["steps"] = env.header_field("ep_steps")[idx].clone()
+    return out
+
+
+@torch.no_grad()
+def run_lookahead(env, scheduler, seed, *, q: Sequence[float] = (25, 50, 75, 100), check_every: int = DECISION_CHECK_EVERY) -> dict[str, torch.Tensor]:
+    """the parents of a `lookahead.LookaheadScheduler` on `env` play one whole episode under it: parents and children are reset
+    (`seed`: an int - parent number i gets seed + i - or one seed per parent; a child gets its parent's; no other env is touched by
+    the reset), then `scheduler.decide_and_step()` until every parent's episode is over or `scheduler.max_steps` steps are played;
+    the parents' done mask is read every `check_every` decisions (the one device->host sync). Returns the `run_episodes` dict with
+    one row per parent, in the scheduler's order - `evaluation.compare` takes it beside the candidates' own `run_episodes` on the
+    same seeds - plus `winners` i32[decisions, P] (candidate index per decision and parent, -1 = no candidate was valid; rows past
+    `decisions[p]`, the decisions parent p needed, are -1), `decisions` i64[P] and `fallbacks`."""
+    if env.auto_reset:
+        raise ValueError("run_lookahead: the env must not auto-reset (a finished episode's statistics are read from its arena block)")
+    B, dev, P = env.num_envs, env.device, len(scheduler.parents)
+    seeds = [int(seed) + i for i in range(P)] if isinstance(seed, int) else [int(s) for s in seed]
+    if len(seeds) != P:
+        raise ValueError(f"run_lookahead: need one seed per parent ({P}), got {len(seeds)}")
+    per_env, mask = [0] * B, [0] * B
+    per_child = len(scheduler.children) // P
+    for i, p in enumerate(scheduler.parents):
+        per_env[p], mask[p] = seeds[i], 1
+        for c in scheduler.children[i * per_child: (i + 1) * per_child]:
+            per_env[c], mask[c] = seeds[i], 1
+    env.reset(seed=per_env, mask=torch.tensor(mask, dtype=torch.uint8).to(dev))
+    scheduler.reset()
+    idx = torch.tensor(scheduler.parents, dtype=torch.long).to(dev)
+    while scheduler.decisions * scheduler.replan_every < scheduler.max_steps:
+        for _ in range(int(check_every)):
+            scheduler.decide_and_step()
+        if bool(((env.obs_i32[idx, 6] != 0) | (env.obs_i32[idx, 7] != 0)).all()):
+            break
+    parent = torch.zeros(B, dtype=torch.bool, device=dev)
+    parent[idx] = True
+    r = env.job_stats(q, active=parent, want_sorted=True)
+    out = {name: r["stats"][idx, k].clone() for k, name in enumerate(JOB_STATS_COLUMNS)}
+    out["avg_job_duration_s"] = out["avg_completed_job_duration"]
+    out["episode_avg_job_duration_s"] = out["avg_job_duration"] * 1e-3
+    out["pct"], out["sorted"] = r["pct"][idx].clone(), r["sorted"][idx].clone()
+    out["q"] = torch.tensor([float(x) for x in q], dtype=torch.float64)
+    out["ok"] = ((env.header_field("terminated") != 0) & (env.obs_i32[:, 7] == 0))[idx].clone()
+    out["steps"] = env.header_field("ep_steps")[idx].clone()
+    out["decisions"] = (out["steps"].long() + scheduler.replan_every - 1) // scheduler.replan_every
+    w = scheduler.winners().clone()
+    late = torch.arange(w.shape[0], device=dev)[:, None] >= out["decisions"][None, :]
+    out["winners"] = torch.where(late, torch.full_like(w, -1), w)
+    out["fallbacks"] = int((out["winners"][~late] == -1).sum()) if w.numel() else 0
     return out
 
 

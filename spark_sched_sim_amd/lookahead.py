@@ -1,0 +1,150 @@
+"""A scheduler that looks ahead: at every decision it forks the env's state once per candidate, plays every copy to the end of the
+episode on the device, and acts as the cheapest one says - the rollout / policy-switching construction (Bertsekas, Tsitsiklis & Wu,
+"Rollout algorithms for combinatorial optimization", J. Heuristics 1997; Chang, Givan & Chong, "Parallel rollout for online solution
+of partially observable Markov decision processes", DEDS 2004) over the heuristics the simulator has on the device. DESIGN.md 12
+describes the construction, why costs are compared at the episode's end only, and its limits.
+
+    env = VecSparkSchedSimEnv(cfg, 2 * (1 + 4), device="cuda:0")
+    sched = LookaheadScheduler(env, parents=[0, 1], candidates=[("fair", 0), ("fifo", 0), ("sjfcp", 0), ("wfair", 1)])
+    r = evaluation.run_lookahead(env, sched, seed=0)
+
+One `decide_and_step()` is four kernel launches and no device->host read:
+    1. `sss_env_copy`        every parent -> its K x S children (K candidates, S samples)
+    2. `sss_rollout_each`    the children to the end of their episodes: candidate k's first step by candidate k, then by candidate k
+                             again (policy switching, `base=None`) or by the base policy (the rollout algorithm, `base=(name, param)`)
+    3. `sss_lookahead_pick`  total job time of every child, mean over a candidate's samples, arg-min -> the parents' policy entries
+    4. `sss_rollout_each`    the parents take `replan_every` steps: the first by the winner, the rest by what the winner's children
+                             played after their first step
+With `reseed=None` a child continues the parent's own future exactly (same generator state), the system is deterministic and every
+policy a function of the state: the best remaining cost never increases from one decision to the next, so the parent ends at or
+below every candidate's own episode cost. With `reseed=int` sample s draws its own task durations - seed = a function of
+(reseed, s, decision number), shared by the K candidates of a parent and by the parents (common random numbers) - and the choice is
+a Monte-Carlo estimate without that guarantee."""
+from __future__ import annotations
+
+from typing import Sequence
+
+import torch
+
+from .binding import POLICY_IDS
+
+_KEYS = ("first_policy", "first_param", "policy", "param")
+_GOLDEN = 0x9E3779B97F4A7C15
+_LOG_ROWS = 1024  # decisions per block of the winners' log
+
+
+def _signed64(x: int) -> int:
+    x &= 2 ** 64 - 1
+    return x - 2 ** 64 if x >= 2 ** 63 else x
+
+
+class LookaheadScheduler:
+    """`parents`: the env ids that are scheduled; `candidates`: [(policy name, param), ...] as `VecSparkSchedSimEnv.policy_actions`
+    takes them; `base`: None = policy switching, (name, param) = the rollout algorithm over that base policy - it must be one of the
+    candidates (then "do what the base does" is among the choices and the result is never worse than the base; ValueError otherwise);
+    `samples` S and `reseed` as above; `replan_every`: steps a parent takes per decision; `max_steps`: bound of a child's steps (a
+    child it cuts short is invalid and its candidate cannot win); `children`: the P x K x S env ids of the copies in [parent][candidate]
+    [sample] order, default: the ids that follow the largest parent id. The env needs P * (1 + K * S) slots; a clash between
+    parents and children, ids outside the env or too few slots raise ValueError. The env must not record a timeline.
+    After a decision `last_best` (i32[P], -1: no candidate was valid - the parent then follows candidate 0) and `last_scores`
+    (f64[P, K], NaN: a sample did not finish) are device tensors; `fallbacks` counts the (decision, parent) pairs with best == -1
+    (one device->host read when asked)."""
+
+    def __init__(self, env, parents: Sequence[int], candidates: Sequence[tuple[str, int]], base: tuple[str, int] | None = None, samples: int = 1,
+                 reseed: int | None = None, replan_every: int = 1, max_steps: int = 200_000, children: Sequence[int] | None = None) -> None:
+        self.env = env
+        self.parents = [int(p) for p in parents]
+        self.candidates = [(str(n), int(p)) for n, p in candidates]
+        self.base = (str(base[0]), int(base[1])) if base is not None else None
+        self.samples, self.replan_every, self.max_steps = int(samples), int(replan_every), int(max_steps)
+        self.reseed = None if reseed is None else int(reseed)
+        P, K, S, B, dev = len(self.parents), len(self.candidates), self.samples, env.num_envs, env.device
+        if P < 1 or K < 1 or S < 1 or self.replan_every < 1 or self.max_steps < 1:
+            raise ValueError("LookaheadScheduler: need at least one parent, one candidate, one sample, replan_every >= 1 and max_steps >= 1")
+        if K * S > 1024:
+            raise ValueError(f"LookaheadScheduler: candidates x samples must be at most 1024, got {K} x {S}")
+        if self.reseed is not None and not 0 <= self.reseed < 2 ** 64:
+            raise ValueError("LookaheadScheduler: reseed must be in [0, 2**64)")
+        ids = [(n, p, env._policy_id(n, p)) for n, p in self.candidates]  # (ValueError / KeyError for a name or alpha the env does not have)
+        if self.base is not None and self.base not in self.candidates:
+            raise ValueError(f"LookaheadScheduler: the base policy {self.base} must be one of the candidates {self.candidates}")
+        if len(set(self.parents)) != P or any(not 0 <= p < B for p in self.parents):
+            raise ValueError(f"LookaheadScheduler: parents must be distinct env ids in [0, {B}), got {self.parents}")
+        if B < P * (1 + K * S):
+            raise ValueError(f"LookaheadScheduler: {P} parents x (1 + {K} candidates x {S} samples) need {P * (1 + K * S)} envs, the env has {B}")
+        if children is None:
+            first = max(self.parents) + 1
+            children = list(range(first, first + P * K * S))
+        self.children = [int(c) for c in children]
+        if len(self.children) != P * K * S:
+            raise ValueError(f"LookaheadScheduler: need {P * K * S} children ({P} x {K} x {S}), got {len(self.children)}")
+        if any(not 0 <= c < B for c in self.children):
+            raise ValueError(f"LookaheadScheduler: not enough env slots behind the parents for {P * K * S} children (the env has {B}); pass `children`")
+        if len(set(self.children)) != len(self.children) or set(self.children) & set(self.parents):
+            raise ValueError("LookaheadScheduler: children must be distinct and disjoint from the parents")
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)  # noqa: E731
+        base_id = (self.base[0], self.base[1], env._policy_id(*self.base)) if self.base is not None else None
+        after = [base_id or c for c in ids]  # what candidate k's children play after their first step
+        self._cand = {"first_policy": i32([c[2] for c in ids]), "first_param": i32([c[1] for c in ids]),
+                      "policy": i32([c[2] for c in after]), "param": i32([c[1] for c in after])}
+        self._parents = i32(self.parents)
+        self._children = i32(self.children).reshape(P, K, S).contiguous()
+        self._fork_src = i32([p for p in self.parents for _ in range(K * S)])
+        self._fork_dst = self._children.reshape(-1)
+        # the two launches' per-env policy arrays: the children's are fixed; the parents' are -1 until the pick kernel writes them
+        kid = {k: [-1] * B for k in _KEYS}
+        for n, c in enumerate(self.children):
+            k = (n // S) % K
+            kid["first_policy"][c], kid["first_param"][c], kid["policy"][c], kid["param"][c] = ids[k][2], ids[k][1], after[k][2], after[k][1]
+        self._kid = {k: i32(v) for k, v in kid.items()}
+        self._par = {k: torch.full((B,), -1, dtype=torch.int32, device=dev) for k in _KEYS}
+        mk = lambda: {"steps": torch.zeros(B, dtype=torch.int32, device=dev), "first_stage_idx": torch.full((B,), -1, dtype=torch.int32, device=dev),  # noqa: E731
+                      "first_num_exec": torch.zeros(B, dtype=torch.int32, device=dev)}
+        self.child_out, self.parent_out = mk(), mk()  # what the two `rollout_each` launches of the last decision reported
+        self.last_scores = torch.full((P, K), float("nan"), dtype=torch.float64, device=dev)
+        self._seed_base = None
+        if self.reseed is not None:  # seed(s, d) = reseed + (d * S + s) * GOLDEN mod 2^64 (`seed_for`), computed on the device
+            s_of = torch.arange(S, dtype=torch.int64).repeat(P * K)  # sample index of fork pair n = (p * K + k) * S + s
+            self._seed_base = (s_of * _signed64(_GOLDEN) + _signed64(self.reseed)).to(dev)
+            self._seeds = torch.zeros(P * K * S, dtype=torch.int64, device=dev)
+        self.reset()
+
+    def reset(self) -> None:
+        """forgets the decisions taken so far (the seeds of a reseeded lookahead start over): for a new episode of the parents"""
+        P, dev = len(self.parents), self.env.device
+        self.decisions = 0
+        self._log = [torch.full((_LOG_ROWS, P), -1, dtype=torch.int32, device=dev)]
+        self.last_best = self._log[0][0]
+        for t in self._par.values():
+            t.fill_(-1)
+
+    def seed_for(self, sample: int, decision: int) -> int:
+        """the generator seed of sample `sample`'s children at decision number `decision` (numpy's `default_rng(seed)`), the same
+        for every candidate and every parent; None without `reseed`"""
+        if self.reseed is None:
+            return None
+        return (self.reseed + (int(decision) * self.samples + int(sample)) * _GOLDEN) % 2 ** 64
+
+    def decide_and_step(self) -> None:
+        """one decision for every parent and `replan_every` steps by it: four launches (five with `reseed`: one addition makes the
+        decision's seeds), asynchronous, nothing is read back"""
+        env, d = self.env, self.decisions
+        seeds = None
+        if self._seed_base is not None:
+            seeds = torch.add(self._seed_base, _signed64(d * self.samples * _GOLDEN), out=self._seeds)
+        env._env_copy(None, None, self._fork_src, self._fork_dst, seeds)
+        env.rollout_each(self._kid["policy"], self._kid["param"], self.max_steps, self._kid["first_policy"], self._kid["first_param"], out=self.child_out)
+        if d // _LOG_ROWS >= len(self._log):
+            self._log.append(torch.full_like(self._log[0], -1))
+        self.last_best = self._log[d // _LOG_ROWS][d % _LOG_ROWS]
+        env.lookahead_pick(self._parents, self._children, self._cand, self.last_best, self.last_scores, self._par)
+        env.rollout_each(self._par["policy"], self._par["param"], self.replan_every, self._par["first_policy"], self._par["first_param"], out=self.parent_out)
+        self.decisions = d + 1
+
+    def winners(self) -> torch.Tensor:
+        """the winner of every decision since `reset`, i32[decisions, P] on the device (-1: no valid candidate)"""
+        return torch.cat(self._log)[: self.decisions]
+
+    @property
+    def fallbacks(self) -> int:
+        return int((self.winners() == -1).sum())

@@ -351,6 +351,57 @@ class VecSparkSchedSimEnv:
         self._b.check(self._b.lib.sss_rollout(self._h, pid, int(param), int(n_steps), int(self.auto_reset),
                                               self.seed_stride, self._stream()))
 
+    def _i32_per_env(self, t: torch.Tensor, what: str) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or t.numel() != self.num_envs:
+            raise ValueError(f"{what}: need a contiguous int32 tensor of {self.num_envs} entries on {self.device}")
+        return t
+
+    def rollout_each(self, policy: torch.Tensor, param: torch.Tensor, n_steps: int, first_policy: torch.Tensor | None = None,
+                     first_param: torch.Tensor | None = None, out: dict[str, torch.Tensor] | None = None) -> dict[str, torch.Tensor]:
+        """the fused rollout with a policy per env (include/sss.h sss_rollout_each), one asynchronous launch and no host sync: env i
+        takes up to `n_steps` steps under policy id `policy[i]` with `param[i]` (`binding.POLICY_IDS`; int32 device tensors [B]) and
+        stops at the end of its episode or at an env error - there is no auto-reset here, whatever the env's `auto_reset` says.
+        `policy[i] == -1` leaves env i untouched byte for byte. `first_policy` / `first_param` (both or neither): the policy of
+        the env's first step in this launch where the entry is >= 0. The tensors' values are not read back: an id outside the table
+        or a weighted-fair alpha outside [-4, 4] makes the kernel skip that env and report `steps[i] == -1`.
+        Returns {"steps", "first_stage_idx", "first_num_exec"} (int32 [B], on the device): the steps env i took and the action of
+        its first one. They are fresh tensors (0 / -1 / 0 for envs that took no part) unless `out` - such a dict from an earlier
+        call - is given: then those are written again, and entries of envs that take no part keep what they held.
+        Not available while a timeline is recorded (ValueError)."""
+        B, dev = self.num_envs, self.device
+        pol, par = self._i32_per_env(policy, "rollout_each: policy"), self._i32_per_env(param, "rollout_each: param")
+        if (first_policy is None) != (first_param is None):
+            raise ValueError("rollout_each: first_policy and first_param come together or not at all")
+        fpol = self._i32_per_env(first_policy, "rollout_each: first_policy") if first_policy is not None else None
+        fpar = self._i32_per_env(first_param, "rollout_each: first_param") if first_param is not None else None
+        if out is None:
+            out = {"steps": torch.zeros(B, dtype=torch.int32, device=dev), "first_stage_idx": torch.full((B,), -1, dtype=torch.int32, device=dev),
+                   "first_num_exec": torch.zeros(B, dtype=torch.int32, device=dev)}
+        o = [self._i32_per_env(out[k], f"rollout_each: out[{k!r}]") for k in ("steps", "first_stage_idx", "first_num_exec")]
+        self._b.check(self._b.lib.sss_rollout_each(self._h, pol.data_ptr(), par.data_ptr(), fpol.data_ptr() if fpol is not None else None,
+                                                   fpar.data_ptr() if fpar is not None else None, int(n_steps), o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(),
+                                                   self._stream()))
+        return out
+
+    def lookahead_pick(self, parents: torch.Tensor, children: torch.Tensor, cand: dict[str, torch.Tensor], best: torch.Tensor, scores: torch.Tensor,
+                       env_policy: dict[str, torch.Tensor]) -> None:
+        """the decision of a lookahead from its finished children, one asynchronous launch (include/sss.h sss_lookahead_pick, where
+        cost, score and winner are defined): `parents` i32[P] env ids, `children` i32[P, K, S] env ids, `cand` the candidates'
+        {"first_policy", "first_param", "policy", "param"} i32[K]; writes `best` i32[P] (-1: no valid candidate), `scores` f64[P, K]
+        and the winner's four entries into `env_policy` (the same keys, i32[B]) at the parents' ids - the arguments of the
+        `rollout_each` that steps the parents. All tensors on the env's device, contiguous; nothing is read back."""
+        keys = ("first_policy", "first_param", "policy", "param")
+        if children.dim() != 3 or children.shape[0] != parents.numel():
+            raise ValueError(f"lookahead_pick: children must be [P, K, S] with P = {parents.numel()}, got {tuple(children.shape)}")
+        P, K, S = (int(x) for x in children.shape)
+        for name, t, dt, n in [("parents", parents, torch.int32, P), ("children", children, torch.int32, P * K * S), ("best", best, torch.int32, P),
+                               ("scores", scores, torch.float64, P * K)] + [(f"cand[{k!r}]", cand[k], torch.int32, K) for k in keys]:
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"lookahead_pick: {name} must be a contiguous {dt} tensor of {n} entries on {self.device}")
+        e = [self._i32_per_env(env_policy[k], f"lookahead_pick: env_policy[{k!r}]") for k in keys]
+        self._b.check(self._b.lib.sss_lookahead_pick(self._h, P, K, S, parents.data_ptr(), children.data_ptr(), *(cand[k].data_ptr() for k in keys),
+                                                     best.data_ptr(), scores.data_ptr(), *(t.data_ptr() for t in e), self._stream()))
+
     def decima_graph_on_device(self, active: torch.Tensor | None = None, num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict[str, Any]:
         """`decima_graph` without the device->host round trip: the graph's totals (nodes, edges, jobs, schedulable nodes) stay on
         the device (`g["totals_dev"]`, i64[4]); every array is a buffer of the env at its CAPACITY (num_envs x node_cap nodes, ...),
