@@ -923,6 +923,51 @@ int sss_lookahead_pick(sss_handle* h, int n_parents, int n_candidates, int n_sam
                        const int32_t* cand_param_dev, int32_t* best_dev, double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev,
                        int32_t* env_policy_dev, int32_t* env_param_dev, void* stream);
 
+/* sss_rollout_each with a STOP TIME, for a lookahead whose children do not play to the end of the episode. Everything said of
+ * sss_rollout_each holds per env (policy -1 sits out untouched, a bad policy gives steps = -1, an env over at entry is not staged in,
+ * no auto-reset, the first step's policy), with max_steps in the place of n_steps, and on top of it:
+ *   horizon        a span of simulated time in the simulator's unit, > 0, +inf allowed. T = the env's wall_time at entry + horizon is
+ *                  ONE f64 addition. Before each step the env stops if it is terminated, needs a reset, has taken max_steps, or its
+ *                  wall_time >= T; so the first step is taken (unless rounding swallowed the horizon), and the env stops at the
+ *                  first step boundary at or behind T: it can overshoot T by the length of its last step
+ *   t_stop_dev     out, REQUIRED, f64[num_envs]: T, for every env that takes part - an env that is over at entry included
+ *   rem_work_dev   (nullable) out, f64[num_envs][job_cap]: the env's row is written at exit - zero everywhere, then for every active
+ *                  job j the work it still holds, rem_work[env][j] = sum from 0.0 over j's active stages in ascending stage id of
+ *                  (double)(float)remaining_tasks * (double)most_recent_duration: the value the weighted-fair and SJF-CP policies
+ *                  compute, bit for bit. An env that is over at entry gets a zero row
+ * With horizon = +inf the env's bytes, steps and first action are those of sss_rollout_each(.., n_steps = max_steps, ..).
+ * Refused on the host with -54, before any launch: NULL policy_dev, param_dev or t_stop_dev, one of the first_* pair without the
+ * other, horizon NaN or <= 0, max_steps < 0, and a bound timeline ("not available while a timeline is recorded"). */
+int sss_rollout_until(sss_handle* h, const int32_t* policy_dev, const int32_t* param_dev, const int32_t* first_policy_dev, const int32_t* first_param_dev,
+                      double horizon, int max_steps, int32_t* steps_dev, int32_t* first_stage_dev, int32_t* first_exec_dev, double* t_stop_dev,
+                      double* rem_work_dev, void* stream);
+
+/* sss_lookahead_pick for children that stopped at a time horizon (sss_rollout_until, whose t_stop_dev and rem_work_dev it takes):
+ * the same arguments, scores, winner, fallback and per-env arrays - only a child's validity and cost differ. For child c let w be its
+ * wall_time, T = t_stop_dev[c], n its number of arrived jobs, N = num_executors. The order of every sum is part of the definition.
+ *   valid          err == 0 and (terminated != 0 or w >= T), the id inside [0, num_envs). A child that max_steps stopped short of
+ *                  its horizon is invalid: its cost is NaN and its candidate cannot win
+ *   counted jobs   j < n with t_arrival[j] < T. Arrival times are drawn at reset and are the same in every child of a parent (a
+ *                  reseeded child draws other task durations, not other arrivals), and every valid child has reached T or its end:
+ *                  all children of a parent count the SAME jobs, which is what makes their costs comparable
+ *   tail == 0      (none) cost = ((0.0 + d_0) + d_1) + ... over the counted jobs in id order with
+ *                  d_j = min(t_completed[j], min(T, w)) - t_arrival[j]: every child is charged up to the common time T, nothing beyond
+ *   tail == 1      (srpt) d_j = min(t_completed[j], w) - t_arrival[j], summed the same way: charged up to the child's own stop. Unless
+ *                  the child is terminated a tail is added: W_j = rem_work_dev[c][j] of the counted jobs with t_completed[j] > w,
+ *                  sorted ascending W_(1) <= W_(2) <= ...; p_0 = 0.0, p_i = p_(i-1) + W_(i); tail = ((0.0 + p_1 / N) + p_2 / N) + ...;
+ *                  cost = sum + tail. It is the flow time those jobs would still accrue if the N executors served them as one
+ *                  machine, shortest remaining work first - an estimate that, unlike the total remaining work, tells orderings apart
+ * Knowingly ignored: jobs that arrive in [T, w] compete for executors in a child that overshot T but are not charged; the overshoot
+ * w - T itself is charged under srpt and clipped under none; the tail knows no precedence, no moving delay and no future arrival.
+ * With T = +inf every job counts and every valid child is terminated: both forms give sss_lookahead_pick's cost, bit for bit.
+ * A finite horizon carries NO guarantee: the lookahead may end above its candidates.
+ * Errors as sss_lookahead_pick (-53), plus a NULL t_stop_dev / rem_work_dev and a tail other than 0 or 1. */
+int sss_lookahead_pick_horizon(sss_handle* h, int n_parents, int n_candidates, int n_samples, const int32_t* parent_dev, const int32_t* child_dev,
+                               const int32_t* cand_first_policy_dev, const int32_t* cand_first_param_dev, const int32_t* cand_policy_dev,
+                               const int32_t* cand_param_dev, const double* t_stop_dev, const double* rem_work_dev, int tail, int32_t* best_dev,
+                               double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev, int32_t* env_policy_dev,
+                               int32_t* env_param_dev, void* stream);
+
 const char* sss_last_error(void);
 void sss_destroy(sss_handle* h);
 

@@ -50,6 +50,13 @@ int SSS_LAUNCHER(rollout_each)(const SssKernelArgs& a, int num_envs, const int32
                      first_param_of, n_steps, steps, first_stage, first_exec);
   return (int)hipGetLastError();
 }
+int SSS_LAUNCHER(rollout_until)(const SssKernelArgs& a, int num_envs, const int32_t* policy_of, const int32_t* param_of, const int32_t* first_policy_of,
+                                const int32_t* first_param_of, double horizon, int max_steps, int32_t* steps, int32_t* first_stage, int32_t* first_exec,
+                                double* t_stop, double* rem_work, void* stream) {
+  hipLaunchKernelGGL(SSS_KNAME(sss_rollout_until_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy_of, param_of, first_policy_of,
+                     first_param_of, horizon, max_steps, steps, first_stage, first_exec, t_stop, rem_work);
+  return (int)hipGetLastError();
+}
 #endif
 int SSS_LAUNCHER(rollout)(const SssKernelArgs& a, int num_envs, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride, void* stream) {
   SSS_TL_DISPATCH(rollout(a, num_envs, policy, param, n_steps, auto_reset, seed_stride, stream));

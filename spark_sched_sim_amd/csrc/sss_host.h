@@ -665,22 +665,46 @@ extern "C" int sss_rollout_each(sss_handle* h, const int32_t* policy_dev, const 
   return 0;
 }
 
-extern "C" int sss_lookahead_pick(sss_handle* h, int n_parents, int n_candidates, int n_samples, const int32_t* parent_dev, const int32_t* child_dev,
-                                  const int32_t* cand_first_policy_dev, const int32_t* cand_first_param_dev, const int32_t* cand_policy_dev,
-                                  const int32_t* cand_param_dev, int32_t* best_dev, double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev,
-                                  int32_t* env_policy_dev, int32_t* env_param_dev, void* stream) {
+extern "C" int sss_rollout_until(sss_handle* h, const int32_t* policy_dev, const int32_t* param_dev, const int32_t* first_policy_dev, const int32_t* first_param_dev,
+                                 double horizon, int max_steps, int32_t* steps_dev, int32_t* first_stage_dev, int32_t* first_exec_dev, double* t_stop_dev,
+                                 double* rem_work_dev, void* stream) {
   if (!h) return sss_fail(-1, "NULL argument");
   if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
-  if (n_parents < 0) return sss_fail(-53, "sss_lookahead_pick: n_parents must be >= 0, got " + std::to_string(n_parents));
+  if (!policy_dev) return sss_fail(-54, "sss_rollout_until: policy_dev is NULL");
+  if (!param_dev) return sss_fail(-54, "sss_rollout_until: param_dev is NULL");
+  if ((first_policy_dev != nullptr) != (first_param_dev != nullptr)) return sss_fail(-54, "sss_rollout_until: first_policy_dev and first_param_dev come together or not at all");
+  if (!(horizon > 0.0)) return sss_fail(-54, "sss_rollout_until: horizon must be > 0 (+inf is allowed) and not NaN, got " + std::to_string(horizon));
+  if (max_steps < 0) return sss_fail(-54, "sss_rollout_until: max_steps must be >= 0, got " + std::to_string(max_steps));
+  if (!t_stop_dev) return sss_fail(-54, "sss_rollout_until: t_stop_dev is NULL");
+  if (h->tl.t) return sss_fail(-54, "sss_rollout_until: not available while a timeline is recorded (sss_bind_timeline; this kernel has no recording form)");
+  BeDeviceGuard guard(h->device);
+  const SssKernelArgs ka = sss_args(h);
+  if (int rc = sss_is_wide(h->L.E) ? sss_wide_launch_rollout_until(ka, h->L.num_envs, policy_dev, param_dev, first_policy_dev, first_param_dev, horizon, max_steps, steps_dev,
+                                                                   first_stage_dev, first_exec_dev, t_stop_dev, rem_work_dev, stream)
+                                   : sss_narrow_launch_rollout_until(ka, h->L.num_envs, policy_dev, param_dev, first_policy_dev, first_param_dev, horizon, max_steps, steps_dev,
+                                                                     first_stage_dev, first_exec_dev, t_stop_dev, rem_work_dev, stream))
+    return sss_fail(-30, std::string("rollout launch failed: ") + be_error(rc));
+  return 0;
+}
+
+// the arguments that sss_lookahead_pick and sss_lookahead_pick_horizon share: checked (`who` names the entry point in the message) and
+// put into `r`. 1: nothing to do (n_parents == 0)
+static int sss_lookahead_args(sss_handle* h, const std::string& who, int n_parents, int n_candidates, int n_samples, const int32_t* parent_dev, const int32_t* child_dev,
+                              const int32_t* cand_first_policy_dev, const int32_t* cand_first_param_dev, const int32_t* cand_policy_dev, const int32_t* cand_param_dev,
+                              int32_t* best_dev, double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev, int32_t* env_policy_dev,
+                              int32_t* env_param_dev, SssLookaheadArgs* out) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (n_parents < 0) return sss_fail(-53, who + ": n_parents must be >= 0, got " + std::to_string(n_parents));
   if (n_candidates < 1 || n_samples < 1 || (int64_t)n_candidates * n_samples > SSS_LA_MAX_CHILDREN)
-    return sss_fail(-53, "sss_lookahead_pick: candidates and samples must be >= 1 and their product at most " + std::to_string(SSS_LA_MAX_CHILDREN) + ", got " +
+    return sss_fail(-53, who + ": candidates and samples must be >= 1 and their product at most " + std::to_string(SSS_LA_MAX_CHILDREN) + ", got " +
                              std::to_string(n_candidates) + " x " + std::to_string(n_samples));
-  if (n_parents == 0) return 0;
-  if (!parent_dev || !child_dev) return sss_fail(-53, "sss_lookahead_pick: parent_dev / child_dev is NULL");
-  if (!cand_first_policy_dev || !cand_first_param_dev || !cand_policy_dev || !cand_param_dev) return sss_fail(-53, "sss_lookahead_pick: a candidate array is NULL");
-  if (!best_dev || !score_dev) return sss_fail(-53, "sss_lookahead_pick: best_dev / score_dev is NULL");
-  if (!env_first_policy_dev || !env_first_param_dev || !env_policy_dev || !env_param_dev) return sss_fail(-53, "sss_lookahead_pick: a per-env policy array is NULL");
-  SssLookaheadArgs r;
+  if (n_parents == 0) return 1;
+  if (!parent_dev || !child_dev) return sss_fail(-53, who + ": parent_dev / child_dev is NULL");
+  if (!cand_first_policy_dev || !cand_first_param_dev || !cand_policy_dev || !cand_param_dev) return sss_fail(-53, who + ": a candidate array is NULL");
+  if (!best_dev || !score_dev) return sss_fail(-53, who + ": best_dev / score_dev is NULL");
+  if (!env_first_policy_dev || !env_first_param_dev || !env_policy_dev || !env_param_dev) return sss_fail(-53, who + ": a per-env policy array is NULL");
+  SssLookaheadArgs& r = *out;
   memset(&r, 0, sizeof(r));
   r.js.state = (const uint8_t*)h->B.state, r.js.env_stride = h->L.env_stride, r.js.off_t_arrival = h->L.off_t_arrival, r.js.off_t_completed = h->L.off_t_completed;
   r.js.off_dur_ring = h->L.off_dur_ring, r.js.num_envs = h->L.num_envs, r.js.J_cap = h->L.J_cap;
@@ -688,8 +712,40 @@ extern "C" int sss_lookahead_pick(sss_handle* h, int n_parents, int n_candidates
   r.cand_first_policy = cand_first_policy_dev, r.cand_first_param = cand_first_param_dev, r.cand_policy = cand_policy_dev, r.cand_param = cand_param_dev;
   r.best = best_dev, r.score = score_dev;
   r.env_first_policy = env_first_policy_dev, r.env_first_param = env_first_param_dev, r.env_policy = env_policy_dev, r.env_param = env_param_dev;
+  return 0;
+}
+
+extern "C" int sss_lookahead_pick(sss_handle* h, int n_parents, int n_candidates, int n_samples, const int32_t* parent_dev, const int32_t* child_dev,
+                                  const int32_t* cand_first_policy_dev, const int32_t* cand_first_param_dev, const int32_t* cand_policy_dev,
+                                  const int32_t* cand_param_dev, int32_t* best_dev, double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev,
+                                  int32_t* env_policy_dev, int32_t* env_param_dev, void* stream) {
+  SssLookaheadArgs r;
+  if (int rc = sss_lookahead_args(h, "sss_lookahead_pick", n_parents, n_candidates, n_samples, parent_dev, child_dev, cand_first_policy_dev, cand_first_param_dev,
+                                  cand_policy_dev, cand_param_dev, best_dev, score_dev, env_first_policy_dev, env_first_param_dev, env_policy_dev, env_param_dev, &r))
+    return rc == 1 ? 0 : rc;
   BeDeviceGuard guard(h->device);
   if (int rc = be_launch_lookahead_pick(r, stream)) return sss_fail(-30, std::string("lookahead pick launch failed: ") + be_error(rc));
+  return 0;
+}
+
+extern "C" int sss_lookahead_pick_horizon(sss_handle* h, int n_parents, int n_candidates, int n_samples, const int32_t* parent_dev, const int32_t* child_dev,
+                                          const int32_t* cand_first_policy_dev, const int32_t* cand_first_param_dev, const int32_t* cand_policy_dev,
+                                          const int32_t* cand_param_dev, const double* t_stop_dev, const double* rem_work_dev, int tail, int32_t* best_dev,
+                                          double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev, int32_t* env_policy_dev,
+                                          int32_t* env_param_dev, void* stream) {
+  SssLookaheadHorizonArgs r;
+  memset(&r, 0, sizeof(r));
+  if (tail != SSS_LA_TAIL_NONE && tail != SSS_LA_TAIL_SRPT) return sss_fail(-53, "sss_lookahead_pick_horizon: tail must be 0 (none) or 1 (srpt), got " + std::to_string(tail));
+  int rc = sss_lookahead_args(h, "sss_lookahead_pick_horizon", n_parents, n_candidates, n_samples, parent_dev, child_dev, cand_first_policy_dev, cand_first_param_dev,
+                              cand_policy_dev, cand_param_dev, best_dev, score_dev, env_first_policy_dev, env_first_param_dev, env_policy_dev, env_param_dev, &r.la);
+  if (rc < 0) return rc;
+  if (h->L.J_cap > SSS_MAX_JOBS) return sss_fail(-53, "sss_lookahead_pick_horizon: job capacity beyond the kernel's LDS working set");
+  if (rc == 1) return 0;
+  if (!t_stop_dev) return sss_fail(-53, "sss_lookahead_pick_horizon: t_stop_dev is NULL");
+  if (!rem_work_dev) return sss_fail(-53, "sss_lookahead_pick_horizon: rem_work_dev is NULL");
+  r.t_stop = t_stop_dev, r.rem_work = rem_work_dev, r.tail = tail, r.num_executors = h->L.E;
+  BeDeviceGuard guard(h->device);
+  if (int rc2 = be_launch_lookahead_pick_horizon(r, stream)) return sss_fail(-30, std::string("lookahead pick launch failed: ") + be_error(rc2));
   return 0;
 }
 

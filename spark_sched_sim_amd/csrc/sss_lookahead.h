@@ -99,3 +99,145 @@ static int be_launch_lookahead_pick(const SssLookaheadArgs& a, void* stream) {
   return (int)hipGetLastError();
 }
 #endif
+
+// ---- the same decision from children that stopped at a time horizon (include/sss.h sss_lookahead_pick_horizon) ----------------
+// The children come from sss_rollout_until (csrc/sss_sim_until.h): child c stopped at its wall time w, at or behind the time
+// T = t_stop[c] that all children of a parent share, and rem_work[c][j] is the work its job j still holds. Its cost is what its
+// jobs have been charged so far plus, with tail = srpt, an estimate of what is left. The order of every sum is the definition:
+//   valid      err == 0 and (terminated != 0 or w >= T), the id inside the arena; otherwise NaN (a child that max_steps cut short
+//              of its horizon is invalid, as an unfinished child is to the pick above)
+//   counted    the arrived jobs (j < n of js_env) with t_arrival[j] < T. Arrivals are drawn at reset and shared by every child of a
+//              parent (also under `reseed`, which draws task durations only): the counted set is the SAME for all children of a
+//              parent, which is what makes their costs comparable although they stopped at different wall times
+//   tail none  cost = ((0.0 + d_0) + d_1) + ... over the counted jobs in id order, d_j = min(t_completed[j], min(T, w)) - t_arrival[j]:
+//              every child is charged up to the common time T and nothing beyond
+//   tail srpt  d_j = js_duration(t_arrival[j], t_completed[j], w): charged up to the child's own stop; and, unless the child is
+//              terminated, plus the tail: W_j = rem_work[c][j] of the counted jobs with t_completed[j] > w, sorted ascending
+//              W_(1) <= W_(2) <= ..., p_0 = 0.0, p_i = p_(i-1) + W_(i), tail = ((0.0 + p_1 / N) + p_2 / N) + ..., N = num_executors:
+//              the flow time the unfinished jobs would still accrue if all executors served them as ONE machine, shortest
+//              remaining work first. cost = sum + tail.
+// With T = +inf every job counts and every valid child is terminated: both forms are la_child_cost, bit for bit.
+// Scores, NaN handling, arg-min, ties, the -1 fallback and the per-env arrays are la_score / la_argmin / la_decide.
+// One wavefront per parent again, looping over the parent's children: lanes fill the child's sort keys (LDS, 8 KB) while lane 0
+// walks the chain of the d_j, the wave sorts the keys (js_key / js_compare_exchange, as sss_job_stats does), lane 0 walks the
+// chain of the prefix sums. Latency of K x S such children per parent; the rollouts around it cost orders of magnitude more.
+#define SSS_LA_TAIL_NONE 0
+#define SSS_LA_TAIL_SRPT 1
+
+struct SssLookaheadHorizonArgs {
+  SssLookaheadArgs la;
+  const double* t_stop;    // f64[num_envs]
+  const double* rem_work;  // f64[num_envs][J_cap]
+  int32_t tail, num_executors;
+};
+
+struct LhChild {  // what child c's header says (every field is the same on every lane)
+  bool valid, terminated;
+  int n;
+  double w, T;
+  const double *ta, *tc, *rw;
+};
+SSS_JS_ANY LhChild lh_child(const SssLookaheadHorizonArgs& a, int c) {
+  LhChild ch;
+  ch.valid = false, ch.terminated = false, ch.n = 0, ch.w = 0.0, ch.T = 0.0, ch.ta = ch.tc = ch.rw = nullptr;
+  if (c < 0 || c >= a.la.js.num_envs) return ch;
+  const uint8_t* base = a.la.js.state + (size_t)c * (size_t)a.la.js.env_stride;
+  const SssHdr& h = *(const SssHdr*)base;
+  const JsEnv e = js_env(a.la.js, h);
+  ch.n = e.n, ch.w = e.wall, ch.T = a.t_stop[c], ch.terminated = h.terminated != 0;
+  ch.valid = h.err == 0 && (ch.terminated || ch.w >= ch.T);
+  ch.ta = (const double*)(base + a.la.js.off_t_arrival), ch.tc = (const double*)(base + a.la.js.off_t_completed);
+  ch.rw = a.rem_work + (size_t)c * (size_t)a.la.js.J_cap;
+  return ch;
+}
+// the srpt tail sorts the keys of the child's jobs; a job that is not in it sorts behind every work there is
+SSS_JS_ANY bool lh_unfinished(const LhChild& ch, int j) { return ch.ta[j] < ch.T && ch.tc[j] > ch.w; }
+SSS_JS_ANY uint64_t lh_key(const LhChild& ch, int j) { return lh_unfinished(ch, j) ? js_key(ch.rw[j]) : ~0ull; }
+// the charged part: the counted jobs' d_j in id order; *m: the number of jobs whose keys the tail sorts
+SSS_JS_ANY double lh_sum(const LhChild& ch, int tail, int* m) {
+  const double upto = tail == SSS_LA_TAIL_SRPT ? ch.w : (ch.T < ch.w ? ch.T : ch.w);
+  double total = 0.0;
+  int cnt = 0;
+  for (int j = 0; j < ch.n; j++) {
+    if (!(ch.ta[j] < ch.T)) continue;
+    total = total + js_duration(ch.ta[j], ch.tc[j], upto);
+    cnt += lh_unfinished(ch, j) ? 1 : 0;
+  }
+  *m = cnt;
+  return total;
+}
+SSS_JS_ANY double lh_tail(const uint64_t* sorted_key, int m, int num_executors) {
+  const double N = (double)num_executors;
+  double p = 0.0, tail = 0.0;
+  for (int i = 0; i < m; i++) {
+    p = p + js_unkey(sorted_key[i]);
+    tail = tail + p / N;
+  }
+  return tail;
+}
+
+#if !defined(__HIPCC__)
+static int be_launch_lookahead_pick_horizon(const SssLookaheadHorizonArgs& a, void*) {
+  static thread_local double cost[SSS_LA_MAX_CHILDREN], score[SSS_LA_MAX_CHILDREN];
+  static thread_local uint64_t key[SSS_MAX_JOBS];
+  const int KS = a.la.K * a.la.S;
+  for (int i = 0; i < a.la.n_parents; i++) {
+    for (int c = 0; c < KS; c++) {
+      const LhChild ch = lh_child(a, a.la.child[(size_t)i * KS + c]);
+      if (!ch.valid) {
+        cost[c] = (double)NAN;
+        continue;
+      }
+      int m;
+      const double sum = lh_sum(ch, a.tail, &m);
+      cost[c] = sum;
+      if (a.tail != SSS_LA_TAIL_SRPT || ch.terminated) continue;
+      const int P = js_pow2(ch.n);
+      for (int j = 0; j < P; j++) key[j] = j < ch.n ? lh_key(ch, j) : ~0ull;
+      for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1)
+          for (int t = 0; t < P / 2; t++) js_compare_exchange(key, k, j, t);
+      cost[c] = sum + lh_tail(key, m, a.num_executors);
+    }
+    for (int k = 0; k < a.la.K; k++) score[k] = a.la.score[(size_t)i * a.la.K + k] = la_score(cost + (size_t)k * a.la.S, a.la.S);
+    la_decide(a.la, i, la_argmin(score, a.la.K));
+  }
+  return 0;
+}
+#else
+__global__ __launch_bounds__(64) void sss_lookahead_pick_horizon_kernel(SssLookaheadHorizonArgs a) {
+  __shared__ double cost[SSS_LA_MAX_CHILDREN], score[SSS_LA_MAX_CHILDREN];
+  __shared__ uint64_t key[SSS_MAX_JOBS];
+  const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const int KS = a.la.K * a.la.S;  // <= SSS_LA_MAX_CHILDREN (the host checks)
+  for (int c = 0; c < KS; c++) {   // (everything that steers the loop body is block-uniform: it comes from the child's id and header)
+    const LhChild ch = lh_child(a, a.la.child[(size_t)i * KS + c]);
+    if (!ch.valid) {
+      if (lane == 0) cost[c] = (double)NAN;
+      continue;
+    }
+    const bool sort = a.tail == SSS_LA_TAIL_SRPT && !ch.terminated;
+    const int P = sort ? js_pow2(ch.n) : 0;  // <= 1024: n <= J_cap <= SSS_MAX_JOBS (the host checks J_cap)
+    for (int j = lane; j < P; j += 64) key[j] = j < ch.n ? lh_key(ch, j) : ~0ull;
+    double sum = 0.0;
+    int m = 0;
+    if (lane == 0) sum = lh_sum(ch, a.tail, &m);  // (global loads only: the other lanes meet it at the sort's first barrier)
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = lane; t < P / 2; t += 64) js_compare_exchange(key, k, j, t);
+        __syncthreads();
+      }
+    if (lane == 0) cost[c] = sort ? sum + lh_tail(key, m, a.num_executors) : sum;
+    __syncthreads();  // the keys are free for the next child
+  }
+  __syncthreads();
+  for (int k = lane; k < a.la.K; k += 64) score[k] = a.la.score[(size_t)i * a.la.K + k] = la_score(cost + (size_t)k * a.la.S, a.la.S);
+  __syncthreads();
+  if (lane == 0) la_decide(a.la, i, la_argmin(score, a.la.K));
+}
+static int be_launch_lookahead_pick_horizon(const SssLookaheadHorizonArgs& a, void* stream) {
+  hipLaunchKernelGGL(sss_lookahead_pick_horizon_kernel, dim3((unsigned)a.la.n_parents), dim3(64), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+#endif

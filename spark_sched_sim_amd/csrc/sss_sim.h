@@ -788,6 +788,7 @@ SSS_KERNEL void SSS_KNAME(sss_rollout_heur_kernel)(SssKernelArgs a, int policy, 
 #undef SSS_ROLLOUT_HEURISTICS
 
 #include "sss_sim_each.h"  // the fused rollout with a policy per env (sss_rollout_each): a kernel of its own, and the emulator's launchers of it
+#include "sss_sim_until.h"  // ... and the one that stops at a time horizon and reports the remaining work (sss_rollout_until), likewise
 
 #undef H
 #undef FAIL

@@ -67,7 +67,7 @@ def run_episodes(env, actor, seed, max_steps: int = 200_000, *, param: int = 0, 
 
 @torch.no_grad()
 def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_steps: int = 200_000, *, q: Sequence[float] = (25, 50, 75, 100),
-                  check_every: int = DECISION_CHECK_EVERY, fused: bool = False) -> dict[str, torch.Tensor]:
+                  check_every: int = DECISION_CHECK_EVERY, fused: bool = False, horizon: float | None = None, tail: str = "srpt") -> dict[str, torch.Tensor]:
     """the cost-to-go of env states under an on-device policy: `env.fork(src, dst, reseed)` - `reseed` gives every child its own
     task-duration noise on the parent's job sequence - then ONLY the `dst` envs play to the end of their episodes under `policy` /
     `param` (`VecSparkSchedSimEnv.policy_actions`); every other env sits the launches out (SSS_SKIP_ENV) and keeps its state,
@@ -76,8 +76,15 @@ def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_s
     every `check_every` steps, at most `max_steps` steps are played.
     `fused=True`: the children play in ONE launch of the fused rollout with a policy per env (`env.rollout_each`) instead of a policy
     and a step launch per step of the longest child - the same results, bit for bit, and no done mask to read; not available while
-    the env records a timeline."""
+    the env records a timeline.
+    `horizon` (with `fused=True` only; simulated time, > 0): the children stop that span after the fork instead (`env.rollout_until`);
+    the dict then describes the states they stopped in (`ok`: the episode ENDED without an env error) and also holds `t_stop` f64[n],
+    `rem_work` f64[n, job_cap] and `horizon_cost` f64[n]: the child's cost under `tail` as the horizon pick kernel computes it
+    (`env.lookahead_pick_horizon`; `horizon_cost` below is the definition), NaN for a child that `max_steps` cut short."""
     from .training import SKIP_ENV
+
+    if horizon is not None and not fused:
+        raise ValueError("continuations: a horizon needs fused=True (the lock-step route has no stop time)")
 
     if env.auto_reset:
         raise ValueError("continuations: the env must not auto-reset (a finished child's statistics are read from its arena block)")
@@ -93,7 +100,11 @@ def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_s
     if fused:
         pid = env._policy_id(policy, param)
         sit_out = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        env.rollout_each(torch.where(child, torch.full_like(sit_out, pid), sit_out), torch.where(child, torch.full_like(sit_out, int(param)), sit_out), int(max_steps))
+        pol, par = torch.where(child, torch.full_like(sit_out, pid), sit_out), torch.where(child, torch.full_like(sit_out, int(param)), sit_out)
+        if horizon is None:
+            env.rollout_each(pol, par, int(max_steps))
+        else:
+            until = env.rollout_until(pol, par, float(horizon), int(max_steps))
         t = max_steps
     while t < max_steps:
         for _ in range(min(int(check_every), max_steps - t)):
@@ -111,7 +122,47 @@ def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_s
     out["q"] = torch.tensor([float(x) for x in q], dtype=torch.float64)
     out["ok"] = ((env.header_field("terminated") != 0) & (env.obs_i32[:, 7] == 0))[idx].clone()
     out["steps"] = env.header_field("ep_steps")[idx].clone()
+    if horizon is not None:
+        # every child as the one child of a parent of its own: score = cost / 1. (The decision goes to arrays nobody reads.)
+        n = len(dst_l)
+        ids = idx.to(torch.int32)
+        one = {k: torch.zeros(1, dtype=torch.int32, device=dev) for k in ("first_policy", "first_param", "policy", "param")}
+        scratch = {k: torch.zeros(B, dtype=torch.int32, device=dev) for k in one}
+        cost = torch.zeros((n, 1), dtype=torch.float64, device=dev)
+        env.lookahead_pick_horizon(ids, ids.reshape(n, 1, 1), one, until["t_stop"], until["rem_work"], tail, torch.zeros(n, dtype=torch.int32, device=dev), cost, scratch)
+        out["t_stop"], out["rem_work"], out["horizon_cost"] = until["t_stop"][idx].clone(), until["rem_work"][idx].clone(), cost[:, 0].clone()
     return out
+
+
+def horizon_cost(t_arrival, t_completed, wall: float, t_stop: float, rem_work, num_executors: int, terminated: bool, tail: str = "srpt") -> float:
+    """the cost of ONE child that stopped at a time horizon, in plain Python floats - the definition that
+    `env.lookahead_pick_horizon` (include/sss.h sss_lookahead_pick_horizon) computes on the device, bit for bit; the order of every
+    sum is part of it. `t_arrival` / `t_completed`: the arrived jobs in id order (`env.job_times(i)` up to the header's
+    `next_arrival`; an unfinished job's completion time is inf), `wall`: the child's wall time, `t_stop`: T, the time all children
+    of its parent were to reach, `rem_work[j]`: the work job j still holds (`env.rollout_until`), `terminated`: its episode is over.
+    NaN for a child that is not valid: it neither ended nor reached T. (An env error makes a child invalid as well; the caller
+    knows.) Counted are the jobs that arrived before T - the same jobs in every child of a parent, so the costs are comparable.
+      tail "none": every counted job is charged up to min(T, wall) - nothing beyond the common time T;
+      tail "srpt": up to the child's own `wall`, plus - unless it is terminated - the flow time the unfinished counted jobs would
+                   still accrue if the `num_executors` executors served them as one machine, shortest remaining work first."""
+    T, w = float(t_stop), float(wall)
+    if not (terminated or w >= T):
+        return float("nan")
+    if tail not in ("none", "srpt"):
+        raise ValueError(f"horizon_cost: tail must be 'none' or 'srpt', got {tail!r}")
+    counted = [j for j in range(len(t_arrival)) if float(t_arrival[j]) < T]
+    upto = w if tail == "srpt" else min(T, w)
+    total = 0.0
+    for j in counted:
+        total = total + (min(float(t_completed[j]), upto) - float(t_arrival[j]))
+    if tail == "none" or terminated:
+        return total
+    left = sorted(float(rem_work[j]) for j in counted if float(t_completed[j]) > w)
+    p, rest = 0.0, 0.0
+    for W in left:
+        p = p + W
+        rest = rest + p / float(num_executors)
+    return total + rest
 
 
 @torch.no_grad()

@@ -19,14 +19,20 @@ With `reseed=None` a child continues the parent's own future exactly (same gener
 policy a function of the state: the best remaining cost never increases from one decision to the next, so the parent ends at or
 below every candidate's own episode cost. With `reseed=int` sample s draws its own task durations - seed = a function of
 (reseed, s, decision number), shared by the K candidates of a parent and by the parents (common random numbers) - and the choice is
-a Monte-Carlo estimate without that guarantee."""
+a Monte-Carlo estimate without that guarantee.
+
+`horizon=H` (simulated time, `float("inf")` allowed) bounds the children: launch 2 becomes `sss_rollout_until` - a child stops at the
+first step boundary at or behind (the parent's wall time + H) - and launch 3 `sss_lookahead_pick_horizon`, which charges every
+child for the jobs that arrived before that common time and, with `tail="srpt"`, adds an estimate of what the unfinished ones still
+cost (include/sss.h). The cost of a decision then follows H, not the rest of the episode. A finite horizon is a
+heuristic: the guarantee above does NOT carry over, the parent may end above a candidate's own episode."""
 from __future__ import annotations
 
 from typing import Sequence
 
 import torch
 
-from .binding import POLICY_IDS
+from .binding import LOOKAHEAD_TAILS, POLICY_IDS
 
 _KEYS = ("first_policy", "first_param", "policy", "param")
 _GOLDEN = 0x9E3779B97F4A7C15
@@ -48,16 +54,26 @@ class LookaheadScheduler:
     parents and children, ids outside the env or too few slots raise ValueError. The env must not record a timeline.
     After a decision `last_best` (i32[P], -1: no candidate was valid - the parent then follows candidate 0) and `last_scores`
     (f64[P, K], NaN: a sample did not finish) are device tensors; `fallbacks` counts the (decision, parent) pairs with best == -1
-    (one device->host read when asked)."""
+    (one device->host read when asked).
+    `horizon`: None = children play to the end of their episodes; a float > 0 (`float("inf")` included) = they stop that span of
+    simulated time after the fork and are scored by `tail` ("srpt" or "none", `VecSparkSchedSimEnv.lookahead_pick_horizon`); a child
+    that `max_steps` stops short of its horizon is invalid. `child_out` then also holds `t_stop` and `rem_work`. ValueError for a
+    horizon that is <= 0 or NaN, or an unknown tail."""
 
     def __init__(self, env, parents: Sequence[int], candidates: Sequence[tuple[str, int]], base: tuple[str, int] | None = None, samples: int = 1,
-                 reseed: int | None = None, replan_every: int = 1, max_steps: int = 200_000, children: Sequence[int] | None = None) -> None:
+                 reseed: int | None = None, replan_every: int = 1, max_steps: int = 200_000, children: Sequence[int] | None = None,
+                 horizon: float | None = None, tail: str = "srpt") -> None:
         self.env = env
         self.parents = [int(p) for p in parents]
         self.candidates = [(str(n), int(p)) for n, p in candidates]
         self.base = (str(base[0]), int(base[1])) if base is not None else None
         self.samples, self.replan_every, self.max_steps = int(samples), int(replan_every), int(max_steps)
         self.reseed = None if reseed is None else int(reseed)
+        self.horizon, self.tail = (None if horizon is None else float(horizon)), str(tail)
+        if self.horizon is not None and not self.horizon > 0:
+            raise ValueError(f"LookaheadScheduler: horizon must be > 0 (float('inf') is allowed) or None, got {horizon}")
+        if self.tail not in LOOKAHEAD_TAILS:
+            raise ValueError(f"LookaheadScheduler: tail must be one of {sorted(LOOKAHEAD_TAILS)}, got {tail!r}")
         P, K, S, B, dev = len(self.parents), len(self.candidates), self.samples, env.num_envs, env.device
         if P < 1 or K < 1 or S < 1 or self.replan_every < 1 or self.max_steps < 1:
             raise ValueError("LookaheadScheduler: need at least one parent, one candidate, one sample, replan_every >= 1 and max_steps >= 1")
@@ -100,7 +116,10 @@ class LookaheadScheduler:
         self._par = {k: torch.full((B,), -1, dtype=torch.int32, device=dev) for k in _KEYS}
         mk = lambda: {"steps": torch.zeros(B, dtype=torch.int32, device=dev), "first_stage_idx": torch.full((B,), -1, dtype=torch.int32, device=dev),  # noqa: E731
                       "first_num_exec": torch.zeros(B, dtype=torch.int32, device=dev)}
-        self.child_out, self.parent_out = mk(), mk()  # what the two `rollout_each` launches of the last decision reported
+        self.child_out, self.parent_out = mk(), mk()  # what the two rollout launches of the last decision reported
+        if self.horizon is not None:
+            self.child_out["t_stop"] = torch.zeros(B, dtype=torch.float64, device=dev)
+            self.child_out["rem_work"] = torch.zeros((B, env.dims.job_cap), dtype=torch.float64, device=dev)
         self.last_scores = torch.full((P, K), float("nan"), dtype=torch.float64, device=dev)
         self._seed_base = None
         if self.reseed is not None:  # seed(s, d) = reseed + (d * S + s) * GOLDEN mod 2^64 (`seed_for`), computed on the device
@@ -133,11 +152,19 @@ class LookaheadScheduler:
         if self._seed_base is not None:
             seeds = torch.add(self._seed_base, _signed64(d * self.samples * _GOLDEN), out=self._seeds)
         env._env_copy(None, None, self._fork_src, self._fork_dst, seeds)
-        env.rollout_each(self._kid["policy"], self._kid["param"], self.max_steps, self._kid["first_policy"], self._kid["first_param"], out=self.child_out)
+        if self.horizon is None:
+            env.rollout_each(self._kid["policy"], self._kid["param"], self.max_steps, self._kid["first_policy"], self._kid["first_param"], out=self.child_out)
+        else:
+            env.rollout_until(self._kid["policy"], self._kid["param"], self.horizon, self.max_steps, self._kid["first_policy"], self._kid["first_param"],
+                              out=self.child_out)
         if d // _LOG_ROWS >= len(self._log):
             self._log.append(torch.full_like(self._log[0], -1))
         self.last_best = self._log[d // _LOG_ROWS][d % _LOG_ROWS]
-        env.lookahead_pick(self._parents, self._children, self._cand, self.last_best, self.last_scores, self._par)
+        if self.horizon is None:
+            env.lookahead_pick(self._parents, self._children, self._cand, self.last_best, self.last_scores, self._par)
+        else:
+            env.lookahead_pick_horizon(self._parents, self._children, self._cand, self.child_out["t_stop"], self.child_out["rem_work"], self.tail,
+                                       self.last_best, self.last_scores, self._par)
         env.rollout_each(self._par["policy"], self._par["param"], self.replan_every, self._par["first_policy"], self._par["first_param"], out=self.parent_out)
         self.decisions = d + 1
 

@@ -402,6 +402,59 @@ class VecSparkSchedSimEnv:
         self._b.check(self._b.lib.sss_lookahead_pick(self._h, P, K, S, parents.data_ptr(), children.data_ptr(), *(cand[k].data_ptr() for k in keys),
                                                      best.data_ptr(), scores.data_ptr(), *(t.data_ptr() for t in e), self._stream()))
 
+    def rollout_until(self, policy: torch.Tensor, param: torch.Tensor, horizon: float, max_steps: int, first_policy: torch.Tensor | None = None,
+                      first_param: torch.Tensor | None = None, out: dict[str, torch.Tensor] | None = None) -> dict[str, torch.Tensor]:
+        """`rollout_each` with a stop time (include/sss.h sss_rollout_until), one asynchronous launch and no host sync: env i takes
+        steps under `policy[i]` / `param[i]` until its wall time has reached T = its wall time at entry + `horizon` (simulated time,
+        > 0, `float("inf")` allowed; ValueError otherwise), its episode is over, or it has taken `max_steps` steps. Everything else
+        is `rollout_each`'s: -1 sits out untouched, `first_policy` / `first_param`, `steps == -1` for a bad policy.
+        Returns `rollout_each`'s dict plus `t_stop` (f64[B]: T, for every env that took part) and `rem_work` (f64[B, job_cap]: the
+        work every active job of the state the env stopped in still holds - `schedulers.job_work` of its observation, bit for bit
+        - and 0.0 for every other job). Fresh tensors (zeros) unless `out` - such a dict from an earlier call - is given."""
+        B, dev = self.num_envs, self.device
+        pol, par = self._i32_per_env(policy, "rollout_until: policy"), self._i32_per_env(param, "rollout_until: param")
+        if (first_policy is None) != (first_param is None):
+            raise ValueError("rollout_until: first_policy and first_param come together or not at all")
+        fpol = self._i32_per_env(first_policy, "rollout_until: first_policy") if first_policy is not None else None
+        fpar = self._i32_per_env(first_param, "rollout_until: first_param") if first_param is not None else None
+        if out is None:
+            out = {"steps": torch.zeros(B, dtype=torch.int32, device=dev), "first_stage_idx": torch.full((B,), -1, dtype=torch.int32, device=dev),
+                   "first_num_exec": torch.zeros(B, dtype=torch.int32, device=dev), "t_stop": torch.zeros(B, dtype=torch.float64, device=dev),
+                   "rem_work": torch.zeros((B, self.dims.job_cap), dtype=torch.float64, device=dev)}
+        o = [self._i32_per_env(out[k], f"rollout_until: out[{k!r}]") for k in ("steps", "first_stage_idx", "first_num_exec")]
+        for k, n in (("t_stop", B), ("rem_work", B * self.dims.job_cap)):
+            t = out[k]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"rollout_until: out[{k!r}] must be a contiguous float64 tensor of {n} entries on {dev}")
+        self._b.check(self._b.lib.sss_rollout_until(self._h, pol.data_ptr(), par.data_ptr(), fpol.data_ptr() if fpol is not None else None,
+                                                    fpar.data_ptr() if fpar is not None else None, float(horizon), int(max_steps), o[0].data_ptr(), o[1].data_ptr(),
+                                                    o[2].data_ptr(), out["t_stop"].data_ptr(), out["rem_work"].data_ptr(), self._stream()))
+        return out
+
+    def lookahead_pick_horizon(self, parents: torch.Tensor, children: torch.Tensor, cand: dict[str, torch.Tensor], t_stop: torch.Tensor, rem_work: torch.Tensor,
+                               tail: str, best: torch.Tensor, scores: torch.Tensor, env_policy: dict[str, torch.Tensor]) -> None:
+        """`lookahead_pick` for children that stopped at a time horizon (include/sss.h sss_lookahead_pick_horizon, where validity
+        and cost are defined; `evaluation.horizon_cost` restates the cost in Python floats): `t_stop` f64[B] and `rem_work`
+        f64[B, job_cap] as `rollout_until` wrote them for the children, `tail` "none" or "srpt" (`binding.LOOKAHEAD_TAILS`);
+        everything else as `lookahead_pick`. One asynchronous launch, nothing is read back."""
+        from .binding import LOOKAHEAD_TAILS
+
+        if tail not in LOOKAHEAD_TAILS:
+            raise ValueError(f"lookahead_pick_horizon: tail must be one of {sorted(LOOKAHEAD_TAILS)}, got {tail!r}")
+        keys = ("first_policy", "first_param", "policy", "param")
+        if children.dim() != 3 or children.shape[0] != parents.numel():
+            raise ValueError(f"lookahead_pick_horizon: children must be [P, K, S] with P = {parents.numel()}, got {tuple(children.shape)}")
+        P, K, S = (int(x) for x in children.shape)
+        for name, t, dt, n in [("parents", parents, torch.int32, P), ("children", children, torch.int32, P * K * S), ("best", best, torch.int32, P),
+                               ("scores", scores, torch.float64, P * K), ("t_stop", t_stop, torch.float64, self.num_envs),
+                               ("rem_work", rem_work, torch.float64, self.num_envs * self.dims.job_cap)] + [(f"cand[{k!r}]", cand[k], torch.int32, K) for k in keys]:
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"lookahead_pick_horizon: {name} must be a contiguous {dt} tensor of {n} entries on {self.device}")
+        e = [self._i32_per_env(env_policy[k], f"lookahead_pick_horizon: env_policy[{k!r}]") for k in keys]
+        self._b.check(self._b.lib.sss_lookahead_pick_horizon(self._h, P, K, S, parents.data_ptr(), children.data_ptr(), *(cand[k].data_ptr() for k in keys),
+                                                             t_stop.data_ptr(), rem_work.data_ptr(), LOOKAHEAD_TAILS[tail], best.data_ptr(), scores.data_ptr(),
+                                                             *(t.data_ptr() for t in e), self._stream()))
+
     def decima_graph_on_device(self, active: torch.Tensor | None = None, num_tasks_scale: float = 200.0, work_scale: float = 1e5) -> dict[str, Any]:
         """`decima_graph` without the device->host round trip: the graph's totals (nodes, edges, jobs, schedulable nodes) stay on
         the device (`g["totals_dev"]`, i64[4]); every array is a buffer of the env at its CAPACITY (num_envs x node_cap nodes, ...),

@@ -4,7 +4,10 @@ scheduler gets `--samples` forked children (`evaluation.continuations`: same job
 which play to the end of the episode on the device. Prints each scheduler's cost-to-go - the episode's mean job duration and the
 time-average number of jobs in the system - with a 95 % confidence interval over the samples.
 
-    python tools/lookahead_demo.py [--seed 0] [--at 150] [--samples 64] [--policies fair,fifo,sjfcp,wfair:1]
+    python tools/lookahead_demo.py [--seed 0] [--at 150] [--samples 64] [--policies fair,fifo,sjfcp,wfair:1] [--horizon MS] [--tail srpt|none]
+
+With --horizon the children stop that span of simulated time after the fork (`continuations(fused=True, horizon=...)`); the figures
+describe the states they stopped in, and the cost the horizon lookahead would compare (`evaluation.horizon_cost`) is printed beside them.
 """
 from __future__ import annotations
 
@@ -28,6 +31,8 @@ def main() -> None:
     ap.add_argument("--at", type=int, default=150, help="steps the parent plays before the fork")
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--policies", default="fair,fifo,sjfcp,wfair:1", help="on-device policies, name[:param]")
+    ap.add_argument("--horizon", type=float, default=None, help="the children stop this span of simulated time after the fork")
+    ap.add_argument("--tail", default="srpt", choices=("none", "srpt"))
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     policies = [(p.split(":")[0], int(p.split(":")[1]) if ":" in p else 0) for p in args.policies.split(",")]
@@ -43,6 +48,13 @@ def main() -> None:
     print(f"state: seed {args.seed} after {args.at} steps of 'fair': wall_time {h['wall_time']:.0f} ms, {h['n_active']} jobs active, {h['n_completed']} of {h['J']} completed")
     children = list(range(1, 1 + S))
     for name, param in policies:
+        if args.horizon is not None:
+            r = evaluation.continuations(env, [0] * S, children, name, param=param, reseed=[1000 + k for k in range(S)], fused=True, horizon=args.horizon, tail=args.tail)
+            cost = r["horizon_cost"]
+            cost = cost[~torch.isnan(cost)]
+            print(f"{name + (':' + str(param) if param else ''):10s} horizon {args.horizon:g} / {args.tail}: cost {float(cost.mean()):14.1f} over {cost.numel()} of {S} children, "
+                  f"{int(r['ok'].sum())} ended their episode, {float(r['steps'].double().mean()) - args.at:.0f} steps each")
+            continue
         r = evaluation.continuations(env, [0] * S, children, name, param=param, reseed=[1000 + k for k in range(S)])
         ok = r["ok"]
         n = int(ok.sum())
