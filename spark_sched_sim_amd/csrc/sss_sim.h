@@ -58,6 +58,9 @@
 // scratch below; dynamic part (g_pool, sized by the host, see SssParams::off_*): the ordered
 // active-job list, the job -> cache-slot map, the LDS cache of the ACTIVE jobs' records and stage
 // counters (what the event chain touches on every event), and scratch for set images.
+// Aliased by the observation writer (sss_sim_observe.h, OBS_*): setA, setB, fc_dst, fc_num, rl_old and rl_seq hold its per-job
+// records of a chunk of 64 active jobs. They are scratch of one event-loop round each and the observation is written after the
+// step's last round; whoever makes one of them live across the end of a step has to move the writer's records elsewhere.
 struct alignas(16) SssScratch {
   uint8_t pool8[8];  // the 8-slot table of the pool that is open (pool_open / pool_close)
   uint8_t pool8b[8]; // ... of a second pool staged next to it (pool_pair_stage)
