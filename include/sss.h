@@ -968,6 +968,32 @@ int sss_lookahead_pick_horizon(sss_handle* h, int n_parents, int n_candidates, i
                                double* score_dev, int32_t* env_first_policy_dev, int32_t* env_first_param_dev, int32_t* env_policy_dev,
                                int32_t* env_param_dev, void* stream);
 
+/* sss_rollout_each with DECIMA among the policies: whole episodes of the learned scheduler in one launch, every env at its own pace,
+ * and Decima as a candidate or base policy of a lookahead. Everything said of sss_rollout_each holds per env (policy -1 sits out
+ * untouched, a bad id gives steps = -1, an env over at entry is not staged in, no auto-reset, the first step's policy, the three
+ * outputs), with one more policy id:
+ *   5 (Decima)     legal in policy_dev and in first_policy_dev; its param is ignored. A Decima step is the decision of
+ *                  sss_decima_policy (greedy == 0) or sss_decima_policy_argmax (greedy != 0) on the env's current observation rows,
+ *                  bit for bit, followed by the step of sss_step
+ *   a              the policy kernel's arguments: weights, scales, work space and its six per-env outputs, which serve as the
+ *                  hand-over inside the kernel and hold the env's LAST decision afterwards (an env that took no Decima step keeps
+ *                  what they held). active_dev, stage_scores_dev, exec_scores_dev and prof_dev must be NULL: an env sits out with
+ *                  policy -1, and of per-step scores only the last would survive
+ *   rng_counter    the decision of the env's it-th step IN THIS LAUNCH (it = 0, 1, ..; steps under a heuristic count too) draws
+ *                  with rng_counter + it; rng_seed, env and candidate key the draws as in sss_decima_policy. A lock-step loop that
+ *                  passes rng_counter = c0 + t at its t-th iteration draws the same numbers. Ignored when greedy != 0
+ *   policy_dev, param_dev   both NULL: every env plays Decima; else i32[num_envs] each, as for sss_rollout_each
+ *   first_policy_dev, first_param_dev, n_steps, steps_dev, first_stage_dev, first_exec_dev   as for sss_rollout_each
+ * One workgroup holds the simulator's LDS working set and Decima's (20 bytes per node slot) at once, so env layouts with many node
+ * slots that the two-launch route still takes are refused here.
+ * Refused on the host with -55, before any launch: a NULL a, or a NULL weight, work-space or output pointer in it; a non-NULL
+ * active_dev, stage_scores_dev, exec_scores_dev or prof_dev; one of policy_dev / param_dev or of the first_* pair without the
+ * other; n_steps < 0; a bound timeline ("not available while a timeline is recorded"); an env layout whose LDS working set does
+ * not fit the 160 KB of a workgroup. (Plain parameters, like sss_job_stats.) */
+int sss_rollout_decima(sss_handle* h, const sss_decima_policy_args* a, int greedy, const int32_t* policy_dev, const int32_t* param_dev,
+                       const int32_t* first_policy_dev, const int32_t* first_param_dev, int n_steps, int32_t* steps_dev, int32_t* first_stage_dev,
+                       int32_t* first_exec_dev, void* stream);
+
 const char* sss_last_error(void);
 void sss_destroy(sss_handle* h);
 

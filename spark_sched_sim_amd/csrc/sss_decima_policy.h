@@ -17,7 +17,13 @@
 // Sampling: Gumbel-max with a counter-based uniform stream keyed by (seed, counter, env, candidate)
 // - the reference samples with Python's unseeded `random.choices` (utils.py:19-23), i.e. any exact
 // softmax sampler is faithful; this one needs no prefix sums and is reproducible.
-#pragma once
+//
+// Two parts, each included once per translation unit: the device function decima_policy_wave with what it needs, and - unless
+// SSS_DECIMA_WAVE_ONLY is defined - the kernels and launches built on it. A simulator unit takes the first part alone
+// (csrc/sss_sim_decima.h: the fused Decima rollout inlines the function into a kernel of its own); a unit that also holds the
+// kernels includes this file again without the macro and gets the second part then.
+#ifndef SSS_DECIMA_POLICY_WAVE_PART
+#define SSS_DECIMA_POLICY_WAVE_PART
 
 enum { DP_W_PREP = 0, DP_W_MSG = 992, DP_W_UPD = 2336, DP_W_DAG = 3680, DP_W_GLOB = 5184, DP_W_STAGE = 6528, DP_W_EXEC = 14212,
        DP_W_TOTAL = 20808 };  // float offsets of the packed MLPs inside the staged block (sizes: gnn_mlp_params, 16-byte aligned starts)
@@ -37,8 +43,6 @@ struct SssDecimaPolicyArgs {
   float* exec_scores;   // nullable: f32[B][E], -inf where not allowed
   uint64_t* prof;       // nullable: u64[B][8] shader cycles per phase (analysis, prep, layers, summaries, stage, exec)
 };
-
-SSS_SHARED_DYN(g_dp_lds);
 
 SSS_DEV uint32_t dp_ordered(float v) {
   uint32_t u;
@@ -376,6 +380,12 @@ SSS_DEV void decima_policy_wave(const SssLayout& L, const SssBuffers& B, int E, 
   }
 }
 
+#endif  // SSS_DECIMA_POLICY_WAVE_PART
+
+#if !defined(SSS_DECIMA_WAVE_ONLY) && !defined(SSS_DECIMA_POLICY_KERNEL_PART)
+#define SSS_DECIMA_POLICY_KERNEL_PART
+SSS_SHARED_DYN(g_dp_lds);
+
 SSS_KERNEL void sss_decima_policy_kernel(SssLayout L, SssBuffers B, int E, SssDecimaPolicyArgs d) {
   decima_policy_wave(L, B, E, d, wave_env(), g_dp_lds);
 }
@@ -505,3 +515,4 @@ static int be_launch_decima_policy_argmax(const SssLayout& L, const SssBuffers& 
   return 0;
 }
 #endif
+#endif  // SSS_DECIMA_POLICY_KERNEL_PART

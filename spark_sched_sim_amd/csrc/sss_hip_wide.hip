@@ -57,6 +57,27 @@ int SSS_LAUNCHER(rollout_until)(const SssKernelArgs& a, int num_envs, const int3
                      first_param_of, horizon, max_steps, steps, first_stage, first_exec, t_stop, rem_work);
   return (int)hipGetLastError();
 }
+// the fused rollout with Decima among the policies (csrc/sss_sim_decima.h): the simulator's pool and Decima's work space in one dynamic
+// allocation. More than the default 64 KB of dynamic LDS has to be asked for, per device and kernel (as csrc/sss_hip.hip does for the
+// policy kernels). -1: the working set does not fit a gfx950 workgroup's 160 KB (the host refuses that layout before it gets here)
+int SSS_LAUNCHER(rollout_decima)(const SssKernelArgs& a, int num_envs, int greedy, const int32_t* policy_of, const int32_t* param_of, const int32_t* first_policy_of,
+                                 const int32_t* first_param_of, int n_steps, int32_t* steps, int32_t* first_stage, int32_t* first_exec, const SssDecimaPolicyArgs& d,
+                                 void* stream) {
+  static size_t granted[2][64] = {{0}};
+  const size_t lds = (size_t)decima_rollout_pool_bytes(a);
+  if ((size_t)SSS_STATIC_LDS_BYTES + lds > (size_t)160 * 1024) return -1;
+  auto kernel = greedy ? SSS_KNAME(sss_rollout_decima_argmax_kernel) : SSS_KNAME(sss_rollout_decima_kernel);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  size_t& g = granted[greedy ? 1 : 0][dev & 63];  // per device: the attribute belongs to the device's copy of the kernel
+  if (lds > g) {
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
+    g = lds;
+  }
+  hipLaunchKernelGGL(kernel, dim3(num_envs), dim3(64), lds, (hipStream_t)stream, a, policy_of, param_of, first_policy_of, first_param_of, n_steps, steps, first_stage,
+                     first_exec, d);
+  return (int)hipGetLastError();
+}
 #endif
 int SSS_LAUNCHER(rollout)(const SssKernelArgs& a, int num_envs, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride, void* stream) {
   SSS_TL_DISPATCH(rollout(a, num_envs, policy, param, n_steps, auto_reset, seed_stride, stream));

@@ -816,6 +816,50 @@ static int sss_decima_policy_any(sss_handle* h, const sss_decima_policy_args* g,
 extern "C" int sss_decima_policy(sss_handle* h, const sss_decima_policy_args* g, void* stream) { return sss_decima_policy_any(h, g, stream, false); }
 extern "C" int sss_decima_policy_argmax(sss_handle* h, const sss_decima_policy_args* g, void* stream) { return sss_decima_policy_any(h, g, stream, true); }
 
+// the fused rollout with Decima among the policies (csrc/sss_sim_decima.h): sss_rollout_each's checks, the policy arguments', and the
+// LDS working set of the two together - the simulator's static block and pool plus Decima's 20 bytes per node slot - against the
+// 160 KB of a gfx950 workgroup
+extern "C" int sss_rollout_decima(sss_handle* h, const sss_decima_policy_args* g, int greedy, const int32_t* policy_dev, const int32_t* param_dev,
+                                  const int32_t* first_policy_dev, const int32_t* first_param_dev, int n_steps, int32_t* steps_dev, int32_t* first_stage_dev,
+                                  int32_t* first_exec_dev, void* stream) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (!g) return sss_fail(-55, "sss_rollout_decima: the policy arguments are NULL");
+  if (!g->w_prep_dev || !g->w_msg_dev || !g->w_upd_dev || !g->w_dag_dev || !g->w_glob_dev || !g->w_stage_dev || !g->w_exec_dev)
+    return sss_fail(-55, "sss_rollout_decima: a weight pointer (w_*_dev) is NULL");
+  if (!g->node_scratch_dev || !g->job_scratch_dev) return sss_fail(-55, "sss_rollout_decima: node_scratch_dev / job_scratch_dev is NULL");
+  if (!g->stage_idx_dev || !g->num_exec_dev || !g->stage_sel_dev || !g->job_idx_dev || !g->exec_sel_dev || !g->lgprob_dev)
+    return sss_fail(-55, "sss_rollout_decima: an output pointer of the policy arguments is NULL");
+  if (g->active_dev) return sss_fail(-55, "sss_rollout_decima: active_dev must be NULL (an env sits out with policy -1)");
+  if (g->stage_scores_dev || g->exec_scores_dev) return sss_fail(-55, "sss_rollout_decima: stage_scores_dev / exec_scores_dev must be NULL (only the last step's would survive)");
+  if (g->prof_dev) return sss_fail(-55, "sss_rollout_decima: prof_dev must be NULL");
+  if ((policy_dev != nullptr) != (param_dev != nullptr)) return sss_fail(-55, "sss_rollout_decima: policy_dev and param_dev come together or not at all");
+  if ((first_policy_dev != nullptr) != (first_param_dev != nullptr)) return sss_fail(-55, "sss_rollout_decima: first_policy_dev and first_param_dev come together or not at all");
+  if (n_steps < 0) return sss_fail(-55, "sss_rollout_decima: n_steps must be >= 0, got " + std::to_string(n_steps));
+  if (h->tl.t) return sss_fail(-55, "sss_rollout_decima: not available while a timeline is recorded (sss_bind_timeline; this kernel has no recording form)");
+  if (h->cfg.num_executors > 128) return sss_fail(-55, "sss_rollout_decima: num_executors must be <= 128");
+  const bool wide = sss_is_wide(h->L.E);
+  const int64_t lds = (int64_t)(wide ? sss_wide_static_lds_bytes() : sss_narrow_static_lds_bytes()) + ((h->P.pool_bytes + 15) & ~15) + (((int64_t)20 * h->L.n_cap + 64 + 63) & ~(int64_t)63);
+  if (lds > 160 * 1024 || h->L.n_cap > 65535)
+    return sss_fail(-55, "sss_rollout_decima: the LDS working set does not fit (simulator + Decima need " + std::to_string(lds) + " bytes for " + std::to_string(h->L.n_cap) +
+                             " node slots, a workgroup has " + std::to_string(160 * 1024) + ")");
+  SssDecimaPolicyArgs d;
+  d.active = nullptr, d.num_tasks_scale = g->num_tasks_scale, d.work_scale = g->work_scale, d.slope = g->slope;
+  d.w_prep = g->w_prep_dev, d.w_msg = g->w_msg_dev, d.w_upd = g->w_upd_dev, d.w_dag = g->w_dag_dev, d.w_glob = g->w_glob_dev;
+  d.w_stage = g->w_stage_dev, d.w_exec = g->w_exec_dev, d.node_scratch = g->node_scratch_dev, d.job_scratch = g->job_scratch_dev;
+  d.rng_seed = g->rng_seed, d.rng_counter = g->rng_counter, d.stage_idx = g->stage_idx_dev, d.num_exec = g->num_exec_dev;
+  d.stage_sel = g->stage_sel_dev, d.job_idx = g->job_idx_dev, d.exec_sel = g->exec_sel_dev, d.lgprob = g->lgprob_dev;
+  d.stage_scores = nullptr, d.exec_scores = nullptr, d.prof = nullptr;
+  BeDeviceGuard guard(h->device);
+  const SssKernelArgs ka = sss_args(h);
+  if (int rc = wide ? sss_wide_launch_rollout_decima(ka, h->L.num_envs, greedy != 0, policy_dev, param_dev, first_policy_dev, first_param_dev, n_steps, steps_dev,
+                                                     first_stage_dev, first_exec_dev, d, stream)
+                    : sss_narrow_launch_rollout_decima(ka, h->L.num_envs, greedy != 0, policy_dev, param_dev, first_policy_dev, first_param_dev, n_steps, steps_dev,
+                                                       first_stage_dev, first_exec_dev, d, stream))
+    return sss_fail(-30, std::string("decima rollout launch failed: ") + (rc < 0 ? "the LDS working set does not fit" : be_error(rc)));
+  return 0;
+}
+
 static int sss_decima_sample_any(int n_obs, int which, const sss_decima_sample_args* g, void* stream, bool argmax) {
   if (!g || n_obs < 1 || (which != 0 && which != 1)) return sss_fail(-1, "bad argument");
   if (g->num_executors < 1) return sss_fail(-28, "num_executors must be >= 1");

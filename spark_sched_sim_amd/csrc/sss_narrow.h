@@ -21,6 +21,12 @@ int sss_narrow_launch_rollout_each(const SssKernelArgs& a, int num_envs, const i
 int sss_narrow_launch_rollout_until(const SssKernelArgs& a, int num_envs, const int32_t* policy_of, const int32_t* param_of, const int32_t* first_policy_of,
                                     const int32_t* first_param_of, double horizon, int max_steps, int32_t* steps, int32_t* first_stage, int32_t* first_exec, double* t_stop,
                                     double* rem_work, void* stream);
+// ... and the one with Decima among the policies (csrc/sss_sim_decima.h, likewise; greedy: its arg-max kernel); no recording form.
+// A negative return: the env layout's LDS working set does not fit
+struct SssDecimaPolicyArgs;  // csrc/sss_decima_policy.h
+int sss_narrow_launch_rollout_decima(const SssKernelArgs& a, int num_envs, int greedy, const int32_t* policy_of, const int32_t* param_of, const int32_t* first_policy_of,
+                                    const int32_t* first_param_of, int n_steps, int32_t* steps, int32_t* first_stage, int32_t* first_exec, const SssDecimaPolicyArgs& d,
+                                    void* stream);
 // ... and of the kernels that record the executor timelines (csrc/sss_hip_sim_tl.hip: the same unit compiled with -DSSS_TIMELINE;
 // the launchers above hand over to these when SssKernelArgs::tl is bound)
 int sss_narrow_tl_launch_reset(const SssKernelArgs& a, int num_envs, const uint64_t* seeds, const double* tl, const uint8_t* mask, void* stream);

@@ -973,6 +973,20 @@ class DecimaPolicy(nn.Module):
         lg = torch.log(p.gather(1, col[:, None])[:, 0]) + torch.log(pe.gather(1, k[:, None])[:, 0])
         return {"stage_sel": stage_sel, "job_idx": job_slot, "exec_sel": k, "lgprob": lg, "any_stage": any_stage}
 
+    def _env_workspace(self, env) -> dict[str, Any]:
+        """the per-env policy kernels' work space and outputs for `env` (`act_env`, `rollout_env`): made once per env shape"""
+        B, dev, d = env.num_envs, env.device, env.dims
+        ws = getattr(self, "_ws", None)
+        if ws is None or ws["key"] != (B, d.node_cap, d.job_cap, str(dev)):
+            i32 = lambda: torch.empty(B, dtype=torch.int32, device=dev)  # noqa: E731
+            ws = {"key": (B, d.node_cap, d.job_cap, str(dev)),
+                  "node": torch.empty((B, d.node_cap, 53), dtype=torch.float32, device=dev),
+                  "job": torch.empty((B, d.job_cap, 32), dtype=torch.float32, device=dev),
+                  "stage_idx": i32(), "num_exec": i32(), "stage_sel": i32(), "job_idx": i32(), "exec_sel": i32(),
+                  "lgprob": torch.empty(B, dtype=torch.float32, device=dev)}
+            self._ws = ws
+        return ws
+
     @torch.no_grad()
     def act_env(self, env, counter: int, seed: int = 0, active: torch.Tensor | None = None, want_scores: bool = False,
                 want_prof: bool = False, greedy: bool = False):
@@ -991,15 +1005,7 @@ class DecimaPolicy(nn.Module):
         assert self._use_kernels(), "the fused policy kernel supports the published Decima architecture only"
         w = self._packed_weights()
         B, dev, d = env.num_envs, env.device, env.dims
-        ws = getattr(self, "_ws", None)
-        if ws is None or ws["key"] != (B, d.node_cap, d.job_cap, str(dev)):
-            i32 = lambda: torch.empty(B, dtype=torch.int32, device=dev)  # noqa: E731
-            ws = {"key": (B, d.node_cap, d.job_cap, str(dev)),
-                  "node": torch.empty((B, d.node_cap, 53), dtype=torch.float32, device=dev),
-                  "job": torch.empty((B, d.job_cap, 32), dtype=torch.float32, device=dev),
-                  "stage_idx": i32(), "num_exec": i32(), "stage_sel": i32(), "job_idx": i32(), "exec_sel": i32(),
-                  "lgprob": torch.empty(B, dtype=torch.float32, device=dev)}
-            self._ws = ws
+        ws = self._env_workspace(env)
         out = {}
         if want_scores:
             out["stage_scores"] = torch.full((B, d.node_cap), float("-inf"), dtype=torch.float32, device=dev)
@@ -1020,6 +1026,49 @@ class DecimaPolicy(nn.Module):
         out.update(stage_sel=ws["stage_sel"].long(), job_idx=ws["job_idx"].long(), exec_sel=ws["exec_sel"].long(), lgprob=ws["lgprob"],
                    any_stage=ws["stage_idx"] >= 0)
         return {"stage_idx": ws["stage_idx"], "num_exec": ws["num_exec"]}, out
+
+    @torch.no_grad()
+    def rollout_env(self, env, n_steps: int, *, greedy: bool = True, seed: int = 0, counter: int = 0, policy: torch.Tensor | None = None,
+                    param: torch.Tensor | None = None, first_policy: torch.Tensor | None = None, first_param: torch.Tensor | None = None,
+                    out: dict[str, torch.Tensor] | None = None) -> dict[str, torch.Tensor]:
+        """Decima in the fused rollout (include/sss.h sss_rollout_decima), one asynchronous launch and no host sync: every env of a
+        `VecSparkSchedSimEnv` takes up to `n_steps` steps of `act_env` + `env.step`, bit for bit, at its own pace, and stops at the
+        end of its episode or at an env error (no auto-reset, whatever the env's `auto_reset` says). `greedy`: arg-max decisions;
+        else the decision of an env's t-th step in this launch is `act_env(env, counter + t, seed)`'s draw.
+        `policy` / `param` (int32 device tensors [B], both or neither; default: every env plays Decima) as for `env.rollout_each`
+        with one more id, `binding.POLICY_DECIMA`, whose param is ignored: -1 leaves the env untouched byte for byte, the other ids
+        are the on-device heuristics'. `first_policy` / `first_param` (both or neither): the policy of the env's first step where the
+        entry is >= 0 - Decima included. Returns {"steps", "first_stage_idx", "first_num_exec"} as `env.rollout_each` does (`out`: such
+        a dict to write again). Work space and packed weights are `act_env`'s; an optimizer step is picked up through
+        `invalidate_kernel_weights` as there. Refused (ValueError) while a timeline is recorded and for an env whose node capacity
+        does not leave room for the simulator's and Decima's LDS working sets in one workgroup."""
+        import ctypes
+
+        from .binding import SssDecimaPolicyArgs
+        if getattr(self, "_kb", None) is None:
+            self.bind_kernels(env._b)
+        assert self._use_kernels(), "the fused policy kernel supports the published Decima architecture only"
+        w = self._packed_weights()
+        B, dev = env.num_envs, env.device
+        ws = self._env_workspace(env)
+        if (policy is None) != (param is None):
+            raise ValueError("rollout_env: policy and param come together or not at all")
+        if (first_policy is None) != (first_param is None):
+            raise ValueError("rollout_env: first_policy and first_param come together or not at all")
+        ptr = lambda t, what: env._i32_per_env(t, f"rollout_env: {what}").data_ptr() if t is not None else None  # noqa: E731
+        if out is None:
+            out = {"steps": torch.zeros(B, dtype=torch.int32, device=dev), "first_stage_idx": torch.full((B,), -1, dtype=torch.int32, device=dev),
+                   "first_num_exec": torch.zeros(B, dtype=torch.int32, device=dev)}
+        o = [env._i32_per_env(out[k], f"rollout_env: out[{k!r}]") for k in ("steps", "first_stage_idx", "first_num_exec")]
+        a = SssDecimaPolicyArgs(None, 200.0, 1e5, self._packed[2],
+                                w["prep"].data_ptr(), w["msg"].data_ptr(), w["update"].data_ptr(), w["dag"].data_ptr(), w["glob"].data_ptr(),
+                                w["stage"].data_ptr(), w["exec"].data_ptr(), ws["node"].data_ptr(), ws["job"].data_ptr(),
+                                int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), ws["stage_idx"].data_ptr(), ws["num_exec"].data_ptr(),
+                                ws["stage_sel"].data_ptr(), ws["job_idx"].data_ptr(), ws["exec_sel"].data_ptr(), ws["lgprob"].data_ptr(), None, None, None)
+        self._kb.check(self._kb.lib.sss_rollout_decima(env._h, ctypes.byref(a), int(bool(greedy)), ptr(policy, "policy"), ptr(param, "param"),
+                                                       ptr(first_policy, "first_policy"), ptr(first_param, "first_param"), int(n_steps),
+                                                       o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), env._stream()))
+        return out
 
     @staticmethod
     def env_actions(a: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:

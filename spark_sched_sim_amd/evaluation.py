@@ -29,13 +29,16 @@ def _summarize(env, q: Sequence[float]) -> dict[str, torch.Tensor]:
 
 @torch.no_grad()
 def run_episodes(env, actor, seed, max_steps: int = 200_000, *, param: int = 0, greedy: bool = False, generator: torch.Generator | None = None,
-                 q: Sequence[float] = (25, 50, 75, 100), chunk: int = 200) -> dict[str, torch.Tensor]:
+                 q: Sequence[float] = (25, 50, 75, 100), chunk: int = 200, fused: bool = False) -> dict[str, torch.Tensor]:
     """every env of `env` (no auto-reset) plays one whole episode from `reset(seed=seed)` under `actor`:
       - the name of an on-device policy ("fair", "fifo", "wfair", "sjfcp", "hash") with `param`: fused `env.rollout` launches of
         `chunk` steps, the done mask read after each;
       - a `DecimaPolicy` (`greedy`: arg-max actions - they leave the policy's draw counter alone; else draws from `generator`):
         policy and step launches in lock step, finished or failed envs sit the remaining launches out (SSS_SKIP_ENV), the done
-        mask read every 64 steps.
+        mask read every 64 steps. With `fused=True`: `DecimaPolicy.rollout_env` launches of `chunk` steps instead, the done mask read
+        after each - every env at its own pace, the episodes of the lock-step loop under `one_launch=True` bit for bit (`greedy`), or
+        draws keyed by `generator`'s seed and the policy's draw counter, which advances by the steps played. Not while a timeline
+        is recorded; profiles/fused_decima.md says at which sizes it is the faster route.
     At most `max_steps` steps per env. Returns per-env DEVICE tensors the caller owns: the columns of `env.job_stats`
     (`binding.JOB_STATS_COLUMNS`; `avg_job_duration_s` = the mean over the last <= 200 completed jobs in seconds), `pct` f64[B, len(q)]
     with `q`, `sorted` (the env's sorted job durations, NaN behind them), `ok` (the episode ended without an env error) and `steps`."""
@@ -50,6 +53,17 @@ def run_episodes(env, actor, seed, max_steps: int = 200_000, *, param: int = 0, 
             env.rollout(actor, int(chunk), param)
             if bool(((env.header_field("terminated") != 0) | (env.obs_i32[:, 7] != 0)).all()):
                 break
+        return _summarize(env, q)
+    if fused:
+        c0, t = getattr(actor, "_calls", 0) + 1, 0
+        while t < max_steps:
+            n = min(int(chunk), int(max_steps) - t)
+            actor.rollout_env(env, n, greedy=greedy, seed=generator.initial_seed() if generator is not None else 0, counter=c0 + t)
+            t += n
+            if bool(((env.header_field("terminated") != 0) | (env.obs_i32[:, 7] != 0)).all()):
+                break
+        if not greedy:
+            actor._calls = c0 - 1 + t
         return _summarize(env, q)
     done = torch.zeros(B, dtype=torch.bool, device=dev)
     skip = torch.full((B,), SKIP_ENV, dtype=torch.int32, device=dev)
@@ -66,7 +80,7 @@ def run_episodes(env, actor, seed, max_steps: int = 200_000, *, param: int = 0, 
 
 
 @torch.no_grad()
-def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_steps: int = 200_000, *, q: Sequence[float] = (25, 50, 75, 100),
+def continuations(env, src, dst, policy, param: int = 0, reseed=None, max_steps: int = 200_000, *, q: Sequence[float] = (25, 50, 75, 100),
                   check_every: int = DECISION_CHECK_EVERY, fused: bool = False, horizon: float | None = None, tail: str = "srpt") -> dict[str, torch.Tensor]:
     """the cost-to-go of env states under an on-device policy: `env.fork(src, dst, reseed)` - `reseed` gives every child its own
     task-duration noise on the parent's job sequence - then ONLY the `dst` envs play to the end of their episodes under `policy` /
@@ -80,8 +94,15 @@ def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_s
     `horizon` (with `fused=True` only; simulated time, > 0): the children stop that span after the fork instead (`env.rollout_until`);
     the dict then describes the states they stopped in (`ok`: the episode ENDED without an env error) and also holds `t_stop` f64[n],
     `rem_work` f64[n, job_cap] and `horizon_cost` f64[n]: the child's cost under `tail` as the horizon pick kernel computes it
-    (`env.lookahead_pick_horizon`; `horizon_cost` below is the definition), NaN for a child that `max_steps` cut short."""
+    (`env.lookahead_pick_horizon`; `horizon_cost` below is the definition), NaN for a child that `max_steps` cut short.
+    `policy` may also be a `DecimaPolicy` (with `fused=True` and without a horizon only; ValueError otherwise): the children play its
+    arg-max decisions in one launch of `DecimaPolicy.rollout_env`; `param` is ignored."""
+    from .binding import POLICY_DECIMA
     from .training import SKIP_ENV
+
+    learned = not isinstance(policy, str)
+    if learned and (not fused or horizon is not None):
+        raise ValueError("continuations: a DecimaPolicy plays through the fused route only (fused=True) and has no stop time (horizon=None)")
 
     if horizon is not None and not fused:
         raise ValueError("continuations: a horizon needs fused=True (the lock-step route has no stop time)")
@@ -98,10 +119,12 @@ def continuations(env, src, dst, policy: str, param: int = 0, reseed=None, max_s
     done = ~child
     t = 0
     if fused:
-        pid = env._policy_id(policy, param)
+        pid = POLICY_DECIMA if learned else env._policy_id(policy, param)
         sit_out = torch.full((B,), -1, dtype=torch.int32, device=dev)
         pol, par = torch.where(child, torch.full_like(sit_out, pid), sit_out), torch.where(child, torch.full_like(sit_out, int(param)), sit_out)
-        if horizon is None:
+        if learned:
+            policy.rollout_env(env, int(max_steps), greedy=True, policy=pol, param=par)
+        elif horizon is None:
             env.rollout_each(pol, par, int(max_steps))
         else:
             until = env.rollout_until(pol, par, float(horizon), int(max_steps))

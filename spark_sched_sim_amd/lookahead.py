@@ -25,14 +25,20 @@ a Monte-Carlo estimate without that guarantee.
 first step boundary at or behind (the parent's wall time + H) - and launch 3 `sss_lookahead_pick_horizon`, which charges every
 child for the jobs that arrived before that common time and, with `tail="srpt"`, adds an estimate of what the unfinished ones still
 cost (include/sss.h). The cost of a decision then follows H, not the rest of the episode. A finite horizon is a
-heuristic: the guarantee above does NOT carry over, the parent may end above a candidate's own episode."""
+heuristic: the guarantee above does NOT carry over, the parent may end above a candidate's own episode.
+
+`decima=<DecimaPolicy>` makes the learned scheduler one of the policies: `("decima", 0)` may then stand among `candidates` and as `base`
+- "is my policy better than switching among the heuristics from this state", and the rollout algorithm over a learned base policy.
+It is always the policy's ARG-MAX decision, a function of the state, so with `reseed=None` the guarantee above holds with Decima among
+the candidates. Launches 2 and 4 are then `sss_rollout_decima` (`DecimaPolicy.rollout_env`: the same per-env arrays, policy id 5);
+without a Decima candidate the launches are the ones listed above."""
 from __future__ import annotations
 
 from typing import Sequence
 
 import torch
 
-from .binding import LOOKAHEAD_TAILS, POLICY_IDS
+from .binding import LOOKAHEAD_TAILS, POLICY_DECIMA, POLICY_IDS
 
 _KEYS = ("first_policy", "first_param", "policy", "param")
 _GOLDEN = 0x9E3779B97F4A7C15
@@ -58,12 +64,15 @@ class LookaheadScheduler:
     `horizon`: None = children play to the end of their episodes; a float > 0 (`float("inf")` included) = they stop that span of
     simulated time after the fork and are scored by `tail` ("srpt" or "none", `VecSparkSchedSimEnv.lookahead_pick_horizon`); a child
     that `max_steps` stops short of its horizon is invalid. `child_out` then also holds `t_stop` and `rem_work`. ValueError for a
-    horizon that is <= 0 or NaN, or an unknown tail."""
+    horizon that is <= 0 or NaN, or an unknown tail.
+    `decima`: a `DecimaPolicy` for the env's executor count; with it the name "decima" (param ignored, arg-max decisions) is a policy
+    like the others, as a candidate and as `base`. ValueError for "decima" without it, and for a Decima candidate together with
+    `horizon` (there is no time-bounded Decima child)."""
 
     def __init__(self, env, parents: Sequence[int], candidates: Sequence[tuple[str, int]], base: tuple[str, int] | None = None, samples: int = 1,
                  reseed: int | None = None, replan_every: int = 1, max_steps: int = 200_000, children: Sequence[int] | None = None,
-                 horizon: float | None = None, tail: str = "srpt") -> None:
-        self.env = env
+                 horizon: float | None = None, tail: str = "srpt", decima=None) -> None:
+        self.env, self.decima = env, decima
         self.parents = [int(p) for p in parents]
         self.candidates = [(str(n), int(p)) for n, p in candidates]
         self.base = (str(base[0]), int(base[1])) if base is not None else None
@@ -81,7 +90,13 @@ class LookaheadScheduler:
             raise ValueError(f"LookaheadScheduler: candidates x samples must be at most 1024, got {K} x {S}")
         if self.reseed is not None and not 0 <= self.reseed < 2 ** 64:
             raise ValueError("LookaheadScheduler: reseed must be in [0, 2**64)")
-        ids = [(n, p, env._policy_id(n, p)) for n, p in self.candidates]  # (ValueError / KeyError for a name or alpha the env does not have)
+        self._uses_decima = any(n == "decima" for n, _ in self.candidates + ([self.base] if self.base is not None else []))
+        if self._uses_decima and decima is None:
+            raise ValueError('LookaheadScheduler: the policy "decima" needs decima=<DecimaPolicy>')
+        if self._uses_decima and self.horizon is not None:
+            raise ValueError("LookaheadScheduler: a Decima candidate cannot be combined with a horizon (there is no time-bounded Decima child)")
+        policy_id = lambda n, p: POLICY_DECIMA if n == "decima" else env._policy_id(n, p)  # noqa: E731
+        ids = [(n, p, policy_id(n, p)) for n, p in self.candidates]  # (ValueError / KeyError for a name or alpha the env does not have)
         if self.base is not None and self.base not in self.candidates:
             raise ValueError(f"LookaheadScheduler: the base policy {self.base} must be one of the candidates {self.candidates}")
         if len(set(self.parents)) != P or any(not 0 <= p < B for p in self.parents):
@@ -99,7 +114,7 @@ class LookaheadScheduler:
         if len(set(self.children)) != len(self.children) or set(self.children) & set(self.parents):
             raise ValueError("LookaheadScheduler: children must be distinct and disjoint from the parents")
         i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)  # noqa: E731
-        base_id = (self.base[0], self.base[1], env._policy_id(*self.base)) if self.base is not None else None
+        base_id = (self.base[0], self.base[1], policy_id(*self.base)) if self.base is not None else None
         after = [base_id or c for c in ids]  # what candidate k's children play after their first step
         self._cand = {"first_policy": i32([c[2] for c in ids]), "first_param": i32([c[1] for c in ids]),
                       "policy": i32([c[2] for c in after]), "param": i32([c[1] for c in after])}
@@ -144,6 +159,14 @@ class LookaheadScheduler:
             return None
         return (self.reseed + (int(decision) * self.samples + int(sample)) * _GOLDEN) % 2 ** 64
 
+    def _rollout_each(self, arrays: dict[str, torch.Tensor], n_steps: int, out: dict[str, torch.Tensor]) -> None:
+        """the per-env fused rollout of launches 2 and 4: the kernel that knows Decima when a candidate needs it, else the heuristics' own"""
+        if self._uses_decima:
+            self.decima.rollout_env(self.env, n_steps, greedy=True, policy=arrays["policy"], param=arrays["param"], first_policy=arrays["first_policy"],
+                                    first_param=arrays["first_param"], out=out)
+        else:
+            self.env.rollout_each(arrays["policy"], arrays["param"], n_steps, arrays["first_policy"], arrays["first_param"], out=out)
+
     def decide_and_step(self) -> None:
         """one decision for every parent and `replan_every` steps by it: four launches (five with `reseed`: one addition makes the
         decision's seeds), asynchronous, nothing is read back"""
@@ -153,7 +176,7 @@ class LookaheadScheduler:
             seeds = torch.add(self._seed_base, _signed64(d * self.samples * _GOLDEN), out=self._seeds)
         env._env_copy(None, None, self._fork_src, self._fork_dst, seeds)
         if self.horizon is None:
-            env.rollout_each(self._kid["policy"], self._kid["param"], self.max_steps, self._kid["first_policy"], self._kid["first_param"], out=self.child_out)
+            self._rollout_each(self._kid, self.max_steps, self.child_out)
         else:
             env.rollout_until(self._kid["policy"], self._kid["param"], self.horizon, self.max_steps, self._kid["first_policy"], self._kid["first_param"],
                               out=self.child_out)
@@ -165,7 +188,7 @@ class LookaheadScheduler:
         else:
             env.lookahead_pick_horizon(self._parents, self._children, self._cand, self.child_out["t_stop"], self.child_out["rem_work"], self.tail,
                                        self.last_best, self.last_scores, self._par)
-        env.rollout_each(self._par["policy"], self._par["param"], self.replan_every, self._par["first_policy"], self._par["first_param"], out=self.parent_out)
+        self._rollout_each(self._par, self.replan_every, self.parent_out)
         self.decisions = d + 1
 
     def winners(self) -> torch.Tensor:

@@ -6,7 +6,15 @@ One GPU: `python tools/bench_decima.py --envs 4096`. Several GPUs (config 4 = 81
 `python tools/bench_decima.py --gpus 8 --envs 1024` starts its own ranks (or run it under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1`) - `--envs` is per
 rank, envs are sharded by global id, there is no per-step traffic; the timed region is bracketed by
-barriers and the slowest rank's time is used."""
+barriers and the slowest rank's time is used.
+
+`python tools/bench_decima.py --fused [--fused-envs 256,1024,4096] [--repeats 3]` measures something else: WHOLE greedy episodes
+(no auto-reset, every env from its reset to its end, one GPU), in env-steps/s = steps all envs took / wall time, by three routes -
+lock step on the row-parallel pipeline, lock step with the per-env policy kernel (`one_launch=True`), and the fused kernel
+(`DecimaPolicy.rollout_env`, include/sss.h sss_rollout_decima) - and prints one JSON line per env count. The three routes play the
+same episodes (the one-launch and fused ones bit for bit), so the step counts agree; a lock-step launch waits for its slowest
+env, a fused env runs at its own pace but pays the one-wave policy. Every figure is the median of --repeats timed runs after one
+untimed run."""
 import argparse
 import json
 import os
@@ -25,8 +33,60 @@ AGENT = dict(embed_dim=16,
              policy_mlp_kwargs=dict(hid_dims=[64, 64], act_cls="Tanh"))
 
 
+def bench_fused(a) -> None:
+    from spark_sched_sim_amd import evaluation
+
+    dev = f"cuda:{0 if a.device_index is None else a.device_index}"
+    torch.cuda.set_device(dev)
+    cfg = dict(num_executors=a.executors, job_arrival_cap=a.jobs, job_arrival_rate=4.0e-5, moving_delay=2000.0, warmup_delay=1000.0)
+    torch.manual_seed(0)
+    policy = DecimaPolicy(num_executors=a.executors, **AGENT, state_dict_path=a.checkpoint).to(dev).eval()
+    skip_id = -2147483648  # include/sss.h SSS_SKIP_ENV
+
+    def lock_step(env, one_launch: bool) -> None:  # evaluation.run_episodes' loop with the route chosen
+        done = torch.zeros(env.num_envs, dtype=torch.bool, device=dev)
+        skip = torch.full((env.num_envs,), skip_id, dtype=torch.int32, device=dev)
+        for t in range(a.max_steps):
+            act, _ = policy.schedule_env(env, active=~done, greedy=True, one_launch=one_launch)
+            env.step_async(torch.where(done, skip, act["stage_idx"]).contiguous(), act["num_exec"])
+            done = done | (env.obs_i32[:, 6] != 0) | (env.obs_i32[:, 7] != 0)
+            if t % evaluation.DECISION_CHECK_EVERY == evaluation.DECISION_CHECK_EVERY - 1 and bool(done.all()):
+                break
+
+    routes = {"lock_step_rows": lambda env: lock_step(env, False), "lock_step_one_launch": lambda env: lock_step(env, True),
+              "fused": lambda env: policy.rollout_env(env, a.max_steps, greedy=True)}
+    for n in [int(x) for x in a.fused_envs.split(",")]:
+        env = VecSparkSchedSimEnv(cfg, n, device=dev)
+        row = {"metric": "env-steps/s over whole greedy Decima episodes", "envs": n, "executors": a.executors, "jobs": a.jobs, "repeats": a.repeats, "routes": {}}
+        for name in a.routes.split(","):
+            play = routes[name]
+            times, steps, unfinished = [], 0, 0
+            for rep in range(a.repeats + 1):  # (the first run is not timed)
+                env.reset(seed=1000)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                play(env)
+                torch.cuda.synchronize()
+                if rep:
+                    times.append(time.perf_counter() - t0)
+                steps = int(env.header_field("ep_steps").sum())
+                unfinished = int(((env.header_field("terminated") == 0) | (env.obs_i32[:, 7] != 0)).sum())
+            times.sort()
+            med = times[len(times) // 2]
+            row["routes"][name] = {"value": steps / med, "wall_s": med, "wall_s_all": times, "env_steps": steps, "longest_episode": int(env.header_field("ep_steps").max()),
+                                   "unfinished_or_failed_envs": unfinished}
+        env.close()
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fused", action="store_true", help="whole greedy episodes by three routes: lock step (rows), lock step (one launch), the fused kernel")
+    ap.add_argument("--fused-envs", default="256,1024,4096")
+    ap.add_argument("--routes", default="lock_step_rows,lock_step_one_launch,fused", help="--fused: which of the three routes to time")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--max-steps", type=int, default=20000, help="--fused: bound of an episode's steps")
+    ap.add_argument("--checkpoint", default=None, help="--fused: a DecimaPolicy state dict (default: the randomly initialised policy of seed 0)")
     ap.add_argument("--gpus", type=int, default=1, help="ranks to start when not already under torch.distributed.run")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=100)
@@ -40,6 +100,8 @@ def main():
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--device-index", type=int, default=None)
     a = ap.parse_args()
+    if a.fused:
+        return bench_fused(a)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # start the ranks ourselves (nothing has touched the GPU yet)
         from spark_sched_sim_amd.distributed import launch_ranks
         raise SystemExit(launch_ranks(a.gpus, [osp.abspath(__file__)] + sys.argv[1:]))

@@ -6,12 +6,16 @@ children, the pick kernel, a step of the parents - four launches per decision), 
 
     python tools/lookahead_eval.py [--envs 256] [--samples 1] [--reseed N] [--replan-every 1] [--base name[:param]]
                                    [--policies fair,fifo,sjfcp,wfair:1] [--chunk 64] [--horizon MS[,MS...]] [--tail srpt|none] [--no-full]
+                                   [--decima CHECKPOINT]
 
 Without --reseed the children continue the parent's own future (exact lookahead: never above a candidate's own episode); with it
 every sample draws its own task durations (Monte-Carlo lookahead: what a scheduler that does not know the future can do).
 With --horizon every listed horizon (simulated time; `LookaheadScheduler(horizon=, tail=)`) gets a run of its own beside the
 candidates and the full-episode lookahead (--no-full leaves that one out): the episode's mean job duration and its paired difference
 to the best candidate and to SJF-CP, the children's steps per decision (mean and longest) and the wall time.
+With --decima CHECKPOINT (a state dict of `DecimaPolicy`, the reference's models/decima/model.pt as it is) the learned policy's arg-max
+decisions are one more candidate, "decima" - it may also be the --base - and one more column: its own episodes (`run_episodes(...,
+fused=True)`). Not together with --horizon.
 The parents are handled `--chunk` at a time: a chunk needs chunk * (1 + candidates * samples) env slots."""
 from __future__ import annotations
 
@@ -72,14 +76,23 @@ def main() -> None:
     ap.add_argument("--tail", default="srpt", choices=("none", "srpt"), help="what a child that stopped at its horizon is charged for the rest")
     ap.add_argument("--no-full", action="store_true", help="with --horizon: leave the full-episode lookahead out")
     ap.add_argument("--tag", default=None, help="key of this run in the output file (default: made of the flags); other keys are kept")
+    ap.add_argument("--decima", default=None, metavar="CHECKPOINT", help="a DecimaPolicy state dict: Decima (arg-max) as a candidate and a column of its own")
     args = ap.parse_args()
     cands = [parse_policy(p) for p in args.policies.split(",")]
+    args.policy = None
+    if args.decima:
+        from spark_sched_sim_amd.decima import DecimaPolicy
+        agent = dict(embed_dim=16, gnn_mlp_kwargs=dict(hid_dims=[32, 16], act_cls="LeakyReLU", act_kwargs=dict(negative_slope=0.2)),
+                     policy_mlp_kwargs=dict(hid_dims=[64, 64], act_cls="Tanh"))
+        args.policy = DecimaPolicy(num_executors=C1["num_executors"], **agent, state_dict_path=args.decima).to(args.device).eval()
+        cands = [c for c in cands if c[0] != "decima"] + [("decima", 0)]
     base = parse_policy(args.base) if args.base else None
     N, K, S = args.envs, len(cands), args.samples
     seeds = [args.seed0 + i for i in range(N)]
 
     solo = VecSparkSchedSimEnv(C1, N, device=args.device)
-    results = {label(c): evaluation.run_episodes(solo, c[0], seeds, param=c[1]) for c in cands}
+    results = {label(c): evaluation.run_episodes(solo, args.policy, seeds, greedy=True, fused=True, chunk=4000) if c[0] == "decima"
+               else evaluation.run_episodes(solo, c[0], seeds, param=c[1]) for c in cands}
     solo.close()
 
     horizons = [float(h) for h in args.horizon.split(",")] if args.horizon else []
@@ -132,7 +145,7 @@ def run_lookaheads(env, args, cands, base, seeds, chunk: int, horizon) -> tuple[
     for at in range(0, N, chunk):
         n = min(chunk, N - at)
         sched = CountingScheduler(env, list(range(n)), cands, base=base, samples=S, reseed=args.reseed, replan_every=args.replan_every,
-                                  children=list(range(chunk, chunk + n * K * S)), horizon=horizon, tail=args.tail)
+                                  children=list(range(chunk, chunk + n * K * S)), horizon=horizon, tail=args.tail, decima=args.policy)
         if env.device.type == "cuda":
             torch.cuda.synchronize(env.device)
         t0 = time.perf_counter()
