@@ -994,6 +994,54 @@ int sss_rollout_decima(sss_handle* h, const sss_decima_policy_args* a, int greed
                        const int32_t* first_policy_dev, const int32_t* first_param_dev, int n_steps, int32_t* steps_dev, int32_t* first_stage_dev,
                        int32_t* first_exec_dev, void* stream);
 
+/* The K BEST decisions of the arg-max policy for every env in one launch: what sss_decima_policy_argmax computes, with k winners of
+ * the stage decision instead of one - the candidates of a lookahead over the ACTIONS of a state. The launch shape is the policy
+ * kernel's; the encoder (DAG analysis, embeddings, summaries) and the stage scores run ONCE per env, only the executor-count block
+ * runs per slot.
+ *   a              the policy kernel's arguments: weights, scales, work space; active_dev is honoured. stage_scores_dev,
+ *                  exec_scores_dev, prof_dev and the six single-decision outputs are ignored and may be NULL; so are the rng fields
+ *   k              slots per env, 1..64
+ *   stage_idx_dev  i32[num_envs][k]: slot r (r = 0, 1, ..) holds the schedulable stage with the r-th largest key, as its rank among
+ *                  the env's schedulable rows (the env's action format). The key is score + 0.0f, equal keys go to the lower node
+ *                  index, a NaN or -inf key never enters: the policy's rule, applied r + 1 times with the earlier winners excluded
+ *   num_exec_dev   i32[num_envs][k]: the arg-max executor count for THAT stage's job - the policy's second decision unchanged (the
+ *                  job's cap, the source job capped at the committable count, ties to the lowest count)
+ *   lgprob_dev     f32[num_envs][k]: the policy's log-probability of the (stage, count) pair; the stage term uses the policy's ONE
+ *                  log-sum-exp over all schedulable stages and is not renormalised over the slots
+ *   count_dev      i32[num_envs]: max(1, min(k, number of stages that can enter)) slots are filled. With nothing schedulable, or an
+ *                  empty observation, slot 0 is the policy's (-1, 1, 0.0f) and count is 1. The slots at or behind count hold
+ *                  stage_idx -1, num_exec -1 (the mark of an empty slot, see sss_rollout_action) and lgprob -inf. An env with
+ *                  active == 0 gets count 0 and empty slots only
+ *   exec_scores_dev (nullable) f32[num_envs][k][E]: row r holds the count scores of slot r's job, -inf beyond its cap - the policy's
+ *                  exec_scores row when that job is chosen; -inf throughout for an empty slot
+ * Slot 0 equals sss_decima_policy_argmax's stage_idx, num_exec and lgprob bit for bit.
+ * Refused on the host with -56, before any launch: a NULL a, a NULL weight or work-space pointer in it, a NULL stage_idx_dev,
+ * num_exec_dev, lgprob_dev or count_dev, k outside [1, 64], num_executors > 128. (Plain parameters, like sss_job_stats.) */
+int sss_decima_topk(sss_handle* h, const sss_decima_policy_args* a, int k, int32_t* stage_idx_dev, int32_t* num_exec_dev, float* lgprob_dev,
+                    int32_t* count_dev, float* exec_scores_dev, void* stream);
+
+/* The per-env fused rollouts with a first ACTION per env: "take action a in state s, then follow the policy" - Q(s, a) by Monte
+ * Carlo - in one launch. With a given it is sss_rollout_decima per env (policy id 5 is legal, policy_dev / param_dev both NULL: every
+ * env plays Decima, the 160 KB LDS refusal applies); with a NULL it is sss_rollout_each per env (policy_dev and param_dev required,
+ * id 5 gives steps = -1, the LDS working set is the simulator's alone). Two arrays take the place of the first-policy pair, both
+ * REQUIRED, i32[num_envs]:
+ *   first_exec_in_dev[i] >= 1   the env's first step in this launch takes (first_stage_in_dev[i], first_exec_in_dev[i]) verbatim, as
+ *                  sss_step would; no policy is evaluated. An action the env refuses leaves the env in the error state sss_step
+ *                  leaves it in, ends the env's part in the launch and is not counted in steps_dev. The step is it = 0 of
+ *                  Decima's draw counter: the first decision behind it draws with rng_counter + 1
+ *   first_exec_in_dev[i] == 0   no forced action: the first step is the env's policy's, the call is the existing kernels' for it
+ *   first_exec_in_dev[i] < 0    the env sits out untouched, byte for byte, exactly like policy -1: an empty slot of sss_decima_topk
+ *                  can be handed over unread
+ * Everything else is the two existing calls': -1 sits out, a bad id gives steps = -1, an env that is over at entry is not staged
+ * in, no auto-reset, steps_dev / first_stage_dev / first_exec_dev (the action of the first step TAKEN - the forced one where there
+ * is one) and Decima's hand-over arrays are written as before.
+ * Refused on the host with -57, before any launch: a NULL first_stage_in_dev or first_exec_in_dev; n_steps < 0; a bound timeline
+ * ("not available while a timeline is recorded"); with a NULL: a NULL policy_dev or param_dev; with a given: everything
+ * sss_rollout_decima refuses of it. (Plain parameters, like sss_job_stats.) */
+int sss_rollout_action(sss_handle* h, const sss_decima_policy_args* a, int greedy, const int32_t* policy_dev, const int32_t* param_dev,
+                       const int32_t* first_stage_in_dev, const int32_t* first_exec_in_dev, int n_steps, int32_t* steps_dev, int32_t* first_stage_dev,
+                       int32_t* first_exec_dev, void* stream);
+
 const char* sss_last_error(void);
 void sss_destroy(sss_handle* h);
 

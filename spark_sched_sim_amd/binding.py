@@ -204,7 +204,7 @@ class SssArenaArgs(C.Structure):  # include/sss.h sss_arena_args
 
 EXPORTS = ["sss_query_dims", "sss_create", "sss_bind_buffers", "sss_reset", "sss_step", "sss_step_bounded", "sss_policy", "sss_rollout",
            "sss_decima_graph_build", "sss_decima_layer_lists", "sss_prefix_rows", "sss_decima_policy", "sss_decima_sample", "sss_gnn_launch",
-           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_bind_timeline", "sss_timeline_render", "sss_decima_argmax", "sss_decima_policy_argmax", "sss_job_stats", "sss_env_layout_id", "sss_env_copy", "sss_rollout_each", "sss_lookahead_pick", "sss_rollout_until", "sss_lookahead_pick_horizon", "sss_rollout_decima", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
+           "sss_linear_wgrad_scratch", "sss_linear_wgrad", "sss_mlp_supported", "sss_mlp_recompute_supported", "sss_mlp_split_supported", "sss_mlp_forward", "sss_mlp_backward", "sss_mlp_wgrad_scratch", "sss_mlp_backward_wgrad", "sss_mlp_wgrad_finish", "sss_collect_step", "sss_gnn_encode", "sss_rows_op", "sss_rows_concat", "sss_segment_categorical", "sss_bit_lists", "sss_arena_append", "sss_discounted_returns", "sss_sequence_baselines", "sss_reward_window_update", "sss_differential_returns", "sss_bind_timeline", "sss_timeline_render", "sss_decima_argmax", "sss_decima_policy_argmax", "sss_job_stats", "sss_env_layout_id", "sss_env_copy", "sss_rollout_each", "sss_lookahead_pick", "sss_rollout_until", "sss_lookahead_pick_horizon", "sss_rollout_decima", "sss_decima_topk", "sss_rollout_action", "sss_last_error", "sss_destroy", "sss_abi_sizeof"]
 POLICY_IDS = {"fair": 0, "fifo": 1, "hash": 2, "wfair": 3, "sjfcp": 4}
 POLICY_DECIMA = 5  # sss_rollout_decima only: the learned policy in a per-env policy array (not in POLICY_IDS: sss_policy / sss_rollout / sss_rollout_each refuse it)
 WFAIR_ALPHA_RANGE = (-4, 4)  # sss_policy / sss_rollout: the weighted-fair exponent (param of policy 3)
@@ -282,6 +282,8 @@ class Binding:
         L.sss_lookahead_pick.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13
         L.sss_rollout_until.argtypes = [C.c_void_p] * 5 + [C.c_double, C.c_int] + [C.c_void_p] * 6
         L.sss_rollout_decima.argtypes = [C.c_void_p, C.POINTER(SssDecimaPolicyArgs), C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4
+        L.sss_decima_topk.argtypes = [C.c_void_p, C.POINTER(SssDecimaPolicyArgs), C.c_int] + [C.c_void_p] * 6
+        L.sss_rollout_action.argtypes = [C.c_void_p, C.POINTER(SssDecimaPolicyArgs), C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4
         L.sss_lookahead_pick_horizon.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 7
         L.sss_bit_lists.argtypes = [C.POINTER(SssBitListArgs), C.c_void_p]
         L.sss_arena_append.argtypes = [C.POINTER(SssArenaArgs), C.c_void_p]

@@ -380,6 +380,337 @@ SSS_DEV void decima_policy_wave(const SssLayout& L, const SssBuffers& B, int E, 
   }
 }
 
+// ---- the K best decisions of the arg-max policy (include/sss.h sss_decima_topk) ----------------------------------------------------
+struct SssDecimaTopkArgs {
+  int k;                // slots per env, 1..64
+  int32_t *stage_idx;   // i32[B][k]: rank among the schedulable rows (the env's action format)
+  int32_t *num_exec;    // i32[B][k]: -1 marks an empty slot
+  float* lgprob;        // f32[B][k]
+  int32_t* count;       // i32[B]
+  float* exec_scores;   // nullable: f32[B][k][E]
+};
+
+// decima_policy_wave<true> with k winners instead of one, written BESIDE it: the encoder phases and the executor-count block are that
+// function's text (keep them in step). Sharing them as inlined pieces was tried and made the existing arg-max policy kernel 32 %
+// slower (776 -> 1027 us at 256 envs, another register allocation; profiles/action_lookahead.md), so the kernels that exist keep their code. The encoder runs ONCE;
+// the stage phase is the policy's (the same list, the
+// same per-lane score order and online log-sum-exp, so slot 0's stage term has the policy's bits) and keeps every schedulable
+// stage's key (sc + 0.0f) and score in the first two LDS arrays of the env's block, which the encoder no longer needs - 8 bytes per
+// schedulable stage, indexed by the stage's position in the list = its rank among the schedulable rows = the env's stage_idx. Slot
+// r is then dp_wave_argmax over the keys that are left (strict `>` within a lane and the smallest index across lanes: equal keys go
+// to the lower node; a NaN or -inf key never enters), the winner's key becomes NaN, and the executor-count block of the policy
+// runs for the winner's job. Nothing but the k-loop's executor-count block is paid per slot.
+SSS_DEV void decima_topk_wave(const SssLayout& L, const SssBuffers& B, int E, const SssDecimaPolicyArgs& d, const SssDecimaTopkArgs& t, int env, uint8_t* lds) {
+  constexpr int F = GNN_EMB;
+  const int lane = wave_lane() & 63;
+  const int K = t.k;
+  int32_t* o_stage = t.stage_idx + (size_t)env * K;
+  int32_t* o_exec = t.num_exec + (size_t)env * K;
+  float* o_lg = t.lgprob + (size_t)env * K;
+  float* o_rows = t.exec_scores ? t.exec_scores + (size_t)env * K * E : nullptr;
+  // slots [from, K) are empty
+  auto pad = [&](int from) {
+    for (int r = from + lane; r < K; r += 64) o_stage[r] = -1, o_exec[r] = -1, o_lg[r] = -__builtin_inff();
+    if (o_rows)
+      for (int q = from * E + lane; q < K * E; q += 64) o_rows[q] = -__builtin_inff();
+  };
+  // nothing to choose from: the policy's own (-1, 1, 0.0f) in slot 0
+  auto nothing = [&]() {
+    if (lane == 0) o_stage[0] = -1, o_exec[0] = 1, o_lg[0] = 0.0f, t.count[env] = 1;
+    if (o_rows)
+      for (int q = lane; q < E; q += 64) o_rows[q] = -__builtin_inff();
+    pad(1);
+  };
+  const int32_t* oi = B.obs_i32 + (size_t)env * SSS_OBS_I32;
+  if (d.active != nullptr && d.active[env] == 0) {  // wave-uniform
+    if (lane == 0) t.count[env] = 0;
+    pad(0);
+    return;
+  }
+  const int n = oi[OBS_N_NODES], ne = oi[OBS_N_EDGES], A = oi[OBS_N_JOBS];
+  if (n == 0 || A == 0) {  // wave-uniform
+    nothing();
+    return;
+  }
+  int ncommit = oi[OBS_NUM_COMMITTABLE], src_idx = oi[OBS_SOURCE_JOB_IDX];
+  const float* nodes = B.nodes + (size_t)env * L.n_cap * 3;
+  const int32_t* el = B.edge_links + (size_t)env * L.ed_cap * 2;
+  const int32_t* dag_ptr = B.dag_ptr + (size_t)env * (L.J_cap + 1);
+  const int32_t* sup = B.exec_supplies + (size_t)env * L.J_cap;
+  float* NS = d.node_scratch + (size_t)env * L.n_cap * DP_NODE_FLOATS;
+  float* JS = d.job_scratch + (size_t)env * L.J_cap * DP_JOB_FLOATS;
+  int32_t* gen = (int32_t*)lds;
+  uint32_t* memb = (uint32_t*)(lds + (size_t)4 * L.n_cap);
+  uint32_t* recv = (uint32_t*)(lds + (size_t)8 * L.n_cap);
+  uint16_t* ostart = (uint16_t*)(lds + (size_t)12 * L.n_cap);
+  uint16_t* oend = (uint16_t*)(lds + (size_t)14 * L.n_cap);
+  uint16_t* njob = (uint16_t*)(lds + (size_t)16 * L.n_cap);
+  uint16_t* list = (uint16_t*)(lds + (size_t)18 * L.n_cap);  // compacted row ids of the current phase
+  float* hglob = (float*)(lds + (size_t)20 * L.n_cap);    // 16 floats (L.n_cap is even)
+
+  // ---- DAG analysis (as in sss_decima_graph_kernel) -------------------------------------------
+  for (int i = lane; i < n; i += 64) gen[i] = 0, recv[i] = 0, ostart[i] = 0, oend[i] = 0;
+  wave_sync_local();
+  for (int it = 0; it <= n; it++) {
+    bool moved = false;
+    for (int e = lane; e < ne; e += 64) {
+      int u = el[2 * e], v = el[2 * e + 1];
+      int gu = gen[u] + 1;
+      if (gen[v] < gu) lane_atomic_max_i32(&gen[v], gu), moved = true;
+    }
+    wave_sync_local();
+    if (!wave_ballot(moved)) break;
+  }
+  uint32_t depth = 0;
+  for (int i = lane; i < n; i += 64) {
+    memb[i] = 1u << gen[i];
+    if ((uint32_t)gen[i] > depth) depth = (uint32_t)gen[i];
+    int lo = 0, hi = A;
+    while (hi - lo > 1) {
+      int mid = (lo + hi) >> 1;
+      if (dag_ptr[mid] <= i) lo = mid; else hi = mid;
+    }
+    njob[i] = (uint16_t)lo;
+  }
+  depth = ~wave_min_u32(~depth);
+  wave_sync_local();
+  for (int e = lane; e < ne; e += 64) lane_atomic_or_u32(&memb[el[2 * e + 1]], 1u << gen[el[2 * e]]);
+  wave_sync_local();
+  for (int e = lane; e < ne; e += 64) {
+    int u = el[2 * e], v = el[2 * e + 1];
+    lane_atomic_or_u32(&recv[u], memb[u] & memb[v]);
+    if (e == 0 || el[2 * (e - 1)] != u) ostart[u] = (uint16_t)e;
+    if (e == ne - 1 || el[2 * (e + 1)] != u) oend[u] = (uint16_t)(e + 1);
+  }
+  wave_sync_local();
+
+  // ---- node features, h_init, starting h (scheduler.py:200-209) ----------------------------------
+  for (int i = lane; i < n; i += 64) {
+    int a = njob[i];
+    int supply = sup[a];
+    int gap = E - supply;
+    if (gap < 0) gap = 0;
+    int cap = gap < ncommit ? gap : ncommit;
+    if (a == src_idx) cap = ncommit;
+    float rem = nodes[3 * i], dur = nodes[3 * i + 1];
+    float x[GNN_NF], h2[16];
+    x[0] = (float)((double)cap / (double)E);
+    x[1] = a == src_idx ? 1.0f : -1.0f;
+    x[2] = (float)((double)supply / (double)E);
+    x[3] = rem / d.num_tasks_scale;
+    x[4] = rem * dur / d.work_scale;
+    float* row = NS + (size_t)i * DP_NODE_FLOATS;
+    GNN_UNROLL for (int k = 0; k < GNN_NF; k++) row[DP_X + k] = x[k];
+    gnn_hidden<GNN_NF, 32, 16, 0>(d.w_prep, x, h2, d.slope);
+    gnn_out<GNN_NF, 32, 16, F>(d.w_prep, h2, 1.0f, [&](int o, float v) { row[DP_HINIT + o] = v; });
+    bool par = oend[i] != 0;
+    if (depth == 0 || par) {
+      for (int o = 0; o < F; o++) row[DP_H + o] = depth == 0 ? row[DP_HINIT + o] : 0.0f;
+    } else {
+      float hi_[F];
+      gnn_load<F>(row + DP_HINIT, hi_);
+      gnn_hidden<F, 32, 16, 0>(d.w_upd, hi_, h2, d.slope);
+      gnn_out<F, 32, 16, F>(d.w_upd, h2, 1.0f, [&](int o, float v) { row[DP_H + o] = v; });
+    }
+  }
+  wave_sync_local();
+
+  // ---- message passing, deepest DAG layer first (scheduler.py:211-236) ---------------------------
+  uint64_t lt = bit64(lane) - 1;
+  for (int l = (int)depth - 1; l >= 0; l--) {
+    // the layer's receiving nodes, compacted: the heavy body then runs on full lanes instead of once
+    // per 64-node round that happens to contain a receiver
+    int cnt = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+      int i = i0 + lane;
+      bool on = i < n && ((recv[i] >> l) & 1u);
+      uint64_t bal = wave_ballot(on);
+      if (on) list[cnt + popc64(bal & lt)] = (uint16_t)i;
+      cnt += popc64(bal);
+    }
+    wave_sync_local();
+    for (int k = lane; k < cnt; k += 64) {
+      int i = list[k];
+      float acc[16], x[F], h2[16];
+      GNN_UNROLL for (int k = 0; k < 16; k++) acc[k] = 0.0f;
+      int used = 0;
+      for (int e = ostart[i]; e < (int)oend[i]; e++) {
+        int v = el[2 * e + 1];
+        if (!(((memb[i] & memb[v]) >> l) & 1u)) continue;
+        gnn_load<F>(NS + (size_t)v * DP_NODE_FLOATS + DP_H, x);
+        gnn_hidden<F, 32, 16, 0>(d.w_msg, x, h2, d.slope);
+        GNN_UNROLL for (int k = 0; k < 16; k++) acc[k] += h2[k];
+        used++;
+      }
+      float agg[F];
+      {
+        GNN_FP_CONTRACT
+        const float* W3 = d.w_msg + 32 * F + 32 + 16 * 32 + 16;
+        const float* b3 = W3 + F * 16;
+        GNN_UNROLL for (int o = 0; o < F; o++) {
+          float v = b3[o] * (float)used;
+          GNN_UNROLL for (int k = 0; k < 16; k++) v += W3[o * 16 + k] * acc[k];
+          agg[o] = v;
+        }
+      }
+      gnn_hidden<F, 32, 16, 0>(d.w_upd, agg, h2, d.slope);
+      float* row = NS + (size_t)i * DP_NODE_FLOATS;
+      gnn_out<F, 32, 16, F>(d.w_upd, h2, 1.0f, [&](int o, float v) { row[DP_TMP + o] = row[DP_HINIT + o] + v; });
+    }
+    wave_sync_local();
+    for (int k = lane; k < cnt; k += 64) {
+      float* row = NS + (size_t)list[k] * DP_NODE_FLOATS;
+      for (int o = 0; o < F; o++) row[DP_H + o] = row[DP_TMP + o];
+    }
+    wave_sync_local();
+  }
+
+  // ---- job summaries and the global summary (scheduler.py:246-283) -------------------------------
+  for (int i = lane; i < n; i += 64) {
+    float* row = NS + (size_t)i * DP_NODE_FLOATS;
+    float x[GNN_NF + F], h2[16];
+    gnn_load<GNN_NF>(row + DP_X, x);
+    gnn_load<F>(row + DP_H, x + GNN_NF);
+    gnn_hidden<GNN_NF + F, 32, 16, 0>(d.w_dag, x, h2, d.slope);
+    GNN_UNROLL for (int k = 0; k < 16; k++) row[DP_TMP + k] = h2[k];
+  }
+  wave_sync_local();
+  for (int a = lane; a < A; a += 64) {
+    float acc[16], x[F], h2[16];
+    GNN_UNROLL for (int k = 0; k < 16; k++) acc[k] = 0.0f;
+    int i0 = dag_ptr[a], i1 = dag_ptr[a + 1];
+    for (int i = i0; i < i1; i++) {
+      const float* t = NS + (size_t)i * DP_NODE_FLOATS + DP_TMP;
+      GNN_UNROLL for (int k = 0; k < 16; k++) acc[k] += t[k];
+    }
+    float* jr = JS + (size_t)a * DP_JOB_FLOATS;
+    gnn_out<GNN_NF + F, 32, 16, F>(d.w_dag, acc, (float)(i1 - i0), [&](int o, float v) { jr[o] = v; });
+    gnn_load<F>(jr, x);
+    gnn_hidden<F, 32, 16, 0>(d.w_glob, x, h2, d.slope);
+    GNN_UNROLL for (int k = 0; k < 16; k++) jr[16 + k] = h2[k];
+  }
+  wave_sync_local();
+  {
+    float acc[16];
+    GNN_UNROLL for (int k = 0; k < 16; k++) acc[k] = 0.0f;
+    for (int a = 0; a < A; a++) {
+      const float* t = JS + (size_t)a * DP_JOB_FLOATS + 16;
+      GNN_UNROLL for (int k = 0; k < 16; k++) acc[k] += t[k];
+    }
+    gnn_out<F, 32, 16, F>(d.w_glob, acc, (float)A, [&](int o, float v) { if (lane == 0) hglob[o] = v; });
+  }
+  wave_sync_local();
+
+  float* skey = (float*)gen;    // f32[n_sched]: what a stage still competes with (NaN: taken); the DAG analysis' arrays are free by now
+  float* ssc = (float*)memb;    // f32[n_sched]: its score
+
+  // ---- stage scores, as in decima_policy_wave ------------------------------------------------------
+  float m_run = -__builtin_inff(), s_run = 0.0f;
+  int n_sched = 0;
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    int i = i0 + lane;
+    bool on = i < n && nodes[3 * i + 2] != 0.0f;
+    uint64_t bal = wave_ballot(on);
+    if (on) list[n_sched + popc64(bal & (bit64(lane) - 1))] = (uint16_t)i;
+    n_sched += popc64(bal);
+  }
+  wave_sync_local();
+  for (int k = lane; k < n_sched; k += 64) {
+    int i = list[k];
+    float sc;
+    const float* row = NS + (size_t)i * DP_NODE_FLOATS;
+    float x[GNN_NF + 3 * F], h2[64];
+    gnn_load<GNN_NF>(row + DP_X, x);
+    gnn_load<F>(row + DP_H, x + GNN_NF);
+    gnn_load<F>(JS + (size_t)njob[i] * DP_JOB_FLOATS, x + GNN_NF + F);
+    GNN_UNROLL for (int q = 0; q < F; q++) x[GNN_NF + 2 * F + q] = hglob[q];
+    gnn_hidden<GNN_NF + 3 * F, 64, 64, 1>(d.w_stage, x, h2, 0.0f);
+    gnn_out<GNN_NF + 3 * F, 64, 64, 1>(d.w_stage, h2, 1.0f, [&](int, float v) { sc = v; });
+    skey[k] = sc + 0.0f, ssc[k] = sc;
+    float m_new = sc > m_run ? sc : m_run;
+    s_run = s_run * expf(m_run - m_new) + expf(sc - m_new);
+    m_run = m_new;
+  }
+  float M, dummy;
+  uint32_t dummy_i;
+  dp_wave_argmax(m_run, 0, M, dummy_i);
+  const float S = wave_sum_f32(m_run == -__builtin_inff() ? 0.0f : s_run * expf(m_run - M));
+  wave_sync_local();
+
+  // ---- slot after slot: the best key that is left, then the executor count for its job ---------------
+  int filled = 0;
+  for (int r = 0; r < K; r++) {
+    float best_key = -__builtin_inff(), best_score = 0.0f;
+    uint32_t best_k = 0x7FFFFFFFu;
+    for (int k = lane; k < n_sched; k += 64) {
+      float key = skey[k];
+      if (key > best_key) best_key = key, best_k = (uint32_t)k, best_score = ssc[k];
+    }
+    float kmax;
+    uint32_t sel;
+    dp_wave_argmax(best_key, best_k, kmax, sel);
+    if (wave_ballot(best_k != 0x7FFFFFFFu) == 0) break;  // wave-uniform: no stage is left
+    dp_wave_argmax(best_k == sel ? best_score : -__builtin_inff(), 0, dummy, dummy_i);
+    const float lg_stage = dummy - M - logf(S);
+    if (lane == 0) skey[sel] = __builtin_nanf("");
+    const int a_sel = njob[list[sel]];
+    int cap;
+    {
+      int gap = E - sup[a_sel];
+      if (gap < 0) gap = 0;
+      cap = gap < ncommit ? gap : ncommit;
+      if (a_sel == src_idx) cap = ncommit;
+    }
+    // executor count c lives on lane c & 63, slot c >> 6 (up to 128 executors: two counts per lane)
+    float esc[2] = {-__builtin_inff(), -__builtin_inff()};
+    float ekey = -__builtin_inff(), ebest = -__builtin_inff(), emax = -__builtin_inff();
+    uint32_t ebest_c = (uint32_t)lane;
+    for (int q = 0; q < 2; q++) {
+      int c = lane + 64 * q;
+      if (c >= E) break;
+      float x[GNN_DF + 2 * F + 1], h2[64];
+      gnn_load<GNN_DF>(NS + (size_t)dag_ptr[a_sel] * DP_NODE_FLOATS + DP_X, x);
+      gnn_load<F>(JS + (size_t)a_sel * DP_JOB_FLOATS, x + GNN_DF);
+      GNN_UNROLL for (int k = 0; k < F; k++) x[GNN_DF + F + k] = hglob[k];
+      x[GNN_DF + 2 * F] = (float)c / (float)E;
+      gnn_hidden<GNN_DF + 2 * F + 1, 64, 64, 1>(d.w_exec, x, h2, 0.0f);
+      float v0 = 0.0f;
+      gnn_out<GNN_DF + 2 * F + 1, 64, 64, 1>(d.w_exec, h2, 1.0f, [&](int, float v) { v0 = v; });
+      if (c < cap) esc[q] = v0;
+      if (o_rows) o_rows[(size_t)r * E + c] = esc[q];
+      if (esc[q] != -__builtin_inff()) {
+        float key = dp_key<true>(esc[q], d.rng_seed, d.rng_counter, env, (uint32_t)c, 1);
+        if (key > ekey) ekey = key, ebest = esc[q], ebest_c = (uint32_t)c;
+        if (esc[q] > emax) emax = esc[q];
+      }
+    }
+    bool ok = emax != -__builtin_inff();
+    uint32_t csel;
+    dp_wave_argmax(ekey, ebest_c, kmax, csel);
+    bool any_exec = wave_ballot(ok) != 0;
+    float EM, ES = 0.0f, esel = 0.0f;
+    dp_wave_argmax(emax, 0, EM, dummy_i);
+    if (any_exec) {
+      float part = 0.0f;
+      for (int q = 0; q < 2; q++) part += esc[q] != -__builtin_inff() ? expf(esc[q] - EM) : 0.0f;
+      ES = wave_sum_f32(part);
+      dp_wave_argmax(ok && ebest_c == csel ? ebest : -__builtin_inff(), 0, esel, dummy_i);
+    } else {
+      csel = 0;
+    }
+    const float lg_exec = any_exec ? esel - EM - logf(ES) : 0.0f;
+    if (lane == 0) o_stage[r] = (int32_t)sel, o_exec[r] = (int32_t)csel + 1, o_lg[r] = lg_stage + lg_exec;
+    wave_sync_local();  // the taken key, before the next slot's scan
+    filled = r + 1;
+  }
+  if (filled == 0) {  // wave-uniform: every schedulable stage scored NaN or -inf (or there is none)
+    nothing();
+    return;
+  }
+  if (lane == 0) t.count[env] = filled;
+  pad(filled);
+}
+
 #endif  // SSS_DECIMA_POLICY_WAVE_PART
 
 #if !defined(SSS_DECIMA_WAVE_ONLY) && !defined(SSS_DECIMA_POLICY_KERNEL_PART)
@@ -512,6 +843,10 @@ static int be_launch_decima_argmax(int n_obs, int which, const SssDecimaSampleAr
 }
 static int be_launch_decima_policy_argmax(const SssLayout& L, const SssBuffers& B, int E, const SssDecimaPolicyArgs& d, void*) {
   emu::launch(L.num_envs, [&]() { decima_policy_wave<true>(L, B, E, d, wave_env(), g_dp_lds); });
+  return 0;
+}
+static int be_launch_decima_topk(const SssLayout& L, const SssBuffers& B, int E, const SssDecimaPolicyArgs& d, const SssDecimaTopkArgs& t, void*) {
+  emu::launch(L.num_envs, [&]() { decima_topk_wave(L, B, E, d, t, wave_env(), g_dp_lds); });
   return 0;
 }
 #endif

@@ -78,6 +78,31 @@ int SSS_LAUNCHER(rollout_decima)(const SssKernelArgs& a, int num_envs, int greed
                      first_exec, d);
   return (int)hipGetLastError();
 }
+// the fused rollouts whose first step is a given action (csrc/sss_sim_action.h). d == nullptr: the heuristics' kernel and the
+// simulator's pool alone; else the Decima kernel (greedy: its arg-max form) with the dynamic LDS of rollout_decima above
+int SSS_LAUNCHER(rollout_action)(const SssKernelArgs& a, int num_envs, int greedy, const int32_t* policy_of, const int32_t* param_of, const int32_t* first_stage_in,
+                                 const int32_t* first_exec_in, int n_steps, int32_t* steps, int32_t* first_stage, int32_t* first_exec, const SssDecimaPolicyArgs* d,
+                                 void* stream) {
+  if (!d) {
+    hipLaunchKernelGGL(SSS_KNAME(sss_rollout_action_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy_of, param_of, first_stage_in,
+                       first_exec_in, n_steps, steps, first_stage, first_exec);
+    return (int)hipGetLastError();
+  }
+  static size_t granted[2][64] = {{0}};
+  const size_t lds = (size_t)decima_rollout_pool_bytes(a);
+  if ((size_t)SSS_STATIC_LDS_BYTES + lds > (size_t)160 * 1024) return -1;
+  auto kernel = greedy ? SSS_KNAME(sss_rollout_action_decima_argmax_kernel) : SSS_KNAME(sss_rollout_action_decima_kernel);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  size_t& g = granted[greedy ? 1 : 0][dev & 63];  // per device: the attribute belongs to the device's copy of the kernel
+  if (lds > g) {
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
+    g = lds;
+  }
+  hipLaunchKernelGGL(kernel, dim3(num_envs), dim3(64), lds, (hipStream_t)stream, a, policy_of, param_of, first_stage_in, first_exec_in, n_steps, steps, first_stage,
+                     first_exec, *d);
+  return (int)hipGetLastError();
+}
 #endif
 int SSS_LAUNCHER(rollout)(const SssKernelArgs& a, int num_envs, int policy, int param, int n_steps, int auto_reset, uint64_t seed_stride, void* stream) {
   SSS_TL_DISPATCH(rollout(a, num_envs, policy, param, n_steps, auto_reset, seed_stride, stream));

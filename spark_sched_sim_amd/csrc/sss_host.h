@@ -860,6 +860,82 @@ extern "C" int sss_rollout_decima(sss_handle* h, const sss_decima_policy_args* g
   return 0;
 }
 
+// weights, scales and work space of the policy arguments -> the device functions' form; the caller sets the rest
+static SssDecimaPolicyArgs sss_decima_device_args(const sss_decima_policy_args* g) {
+  SssDecimaPolicyArgs d;
+  memset(&d, 0, sizeof(d));
+  d.num_tasks_scale = g->num_tasks_scale, d.work_scale = g->work_scale, d.slope = g->slope;
+  d.w_prep = g->w_prep_dev, d.w_msg = g->w_msg_dev, d.w_upd = g->w_upd_dev, d.w_dag = g->w_dag_dev, d.w_glob = g->w_glob_dev;
+  d.w_stage = g->w_stage_dev, d.w_exec = g->w_exec_dev, d.node_scratch = g->node_scratch_dev, d.job_scratch = g->job_scratch_dev;
+  d.rng_seed = g->rng_seed, d.rng_counter = g->rng_counter;
+  return d;
+}
+
+// the K best decisions of the arg-max policy (csrc/sss_decima_policy.h decima_topk_wave)
+extern "C" int sss_decima_topk(sss_handle* h, const sss_decima_policy_args* g, int k, int32_t* stage_idx_dev, int32_t* num_exec_dev, float* lgprob_dev,
+                               int32_t* count_dev, float* exec_scores_dev, void* stream) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (!g) return sss_fail(-56, "sss_decima_topk: the policy arguments are NULL");
+  if (!g->w_prep_dev || !g->w_msg_dev || !g->w_upd_dev || !g->w_dag_dev || !g->w_glob_dev || !g->w_stage_dev || !g->w_exec_dev)
+    return sss_fail(-56, "sss_decima_topk: a weight pointer (w_*_dev) is NULL");
+  if (!g->node_scratch_dev || !g->job_scratch_dev) return sss_fail(-56, "sss_decima_topk: node_scratch_dev / job_scratch_dev is NULL");
+  if (!stage_idx_dev || !num_exec_dev || !lgprob_dev || !count_dev) return sss_fail(-56, "sss_decima_topk: an output pointer (stage_idx_dev, num_exec_dev, lgprob_dev, count_dev) is NULL");
+  if (k < 1 || k > 64) return sss_fail(-56, "sss_decima_topk: k must be in [1, 64], got " + std::to_string(k));
+  if (h->cfg.num_executors > 128) return sss_fail(-56, "sss_decima_topk: num_executors must be <= 128");
+  if ((int64_t)20 * h->L.n_cap + 64 > 65536 || h->L.n_cap > 65535) return sss_fail(-25, "node capacity too large for the Decima policy kernel's LDS working set");
+  SssDecimaPolicyArgs d = sss_decima_device_args(g);
+  d.active = g->active_dev;
+  SssDecimaTopkArgs t;
+  t.k = k, t.stage_idx = stage_idx_dev, t.num_exec = num_exec_dev, t.lgprob = lgprob_dev, t.count = count_dev, t.exec_scores = exec_scores_dev;
+  BeDeviceGuard guard(h->device);
+  if (int rc = be_launch_decima_topk(h->L, h->B, h->cfg.num_executors, d, t, stream)) return sss_fail(-30, std::string("decima top-k launch failed: ") + be_error(rc));
+  return 0;
+}
+
+// the fused rollouts whose first step is a given action (csrc/sss_sim_action.h): sss_rollout_each's checks without policy arguments,
+// sss_rollout_decima's with them
+extern "C" int sss_rollout_action(sss_handle* h, const sss_decima_policy_args* g, int greedy, const int32_t* policy_dev, const int32_t* param_dev,
+                                  const int32_t* first_stage_in_dev, const int32_t* first_exec_in_dev, int n_steps, int32_t* steps_dev, int32_t* first_stage_dev,
+                                  int32_t* first_exec_dev, void* stream) {
+  if (!h) return sss_fail(-1, "NULL argument");
+  if (!h->bound) return sss_fail(-22, "sss_bind_buffers has not been called");
+  if (!first_stage_in_dev || !first_exec_in_dev) return sss_fail(-57, "sss_rollout_action: first_stage_in_dev / first_exec_in_dev is NULL");
+  if (n_steps < 0) return sss_fail(-57, "sss_rollout_action: n_steps must be >= 0, got " + std::to_string(n_steps));
+  if (h->tl.t) return sss_fail(-57, "sss_rollout_action: not available while a timeline is recorded (sss_bind_timeline; this kernel has no recording form)");
+  const bool wide = sss_is_wide(h->L.E);
+  SssDecimaPolicyArgs d;
+  if (!g) {
+    if (!policy_dev || !param_dev) return sss_fail(-57, "sss_rollout_action: policy_dev / param_dev is NULL (required without policy arguments)");
+  } else {
+    if (!g->w_prep_dev || !g->w_msg_dev || !g->w_upd_dev || !g->w_dag_dev || !g->w_glob_dev || !g->w_stage_dev || !g->w_exec_dev)
+      return sss_fail(-57, "sss_rollout_action: a weight pointer (w_*_dev) is NULL");
+    if (!g->node_scratch_dev || !g->job_scratch_dev) return sss_fail(-57, "sss_rollout_action: node_scratch_dev / job_scratch_dev is NULL");
+    if (!g->stage_idx_dev || !g->num_exec_dev || !g->stage_sel_dev || !g->job_idx_dev || !g->exec_sel_dev || !g->lgprob_dev)
+      return sss_fail(-57, "sss_rollout_action: an output pointer of the policy arguments is NULL");
+    if (g->active_dev) return sss_fail(-57, "sss_rollout_action: active_dev must be NULL (an env sits out with policy -1 or a negative first_exec_in)");
+    if (g->stage_scores_dev || g->exec_scores_dev) return sss_fail(-57, "sss_rollout_action: stage_scores_dev / exec_scores_dev must be NULL (only the last step's would survive)");
+    if (g->prof_dev) return sss_fail(-57, "sss_rollout_action: prof_dev must be NULL");
+    if ((policy_dev != nullptr) != (param_dev != nullptr)) return sss_fail(-57, "sss_rollout_action: policy_dev and param_dev come together or not at all");
+    if (h->cfg.num_executors > 128) return sss_fail(-57, "sss_rollout_action: num_executors must be <= 128");
+    const int64_t lds = (int64_t)(wide ? sss_wide_static_lds_bytes() : sss_narrow_static_lds_bytes()) + ((h->P.pool_bytes + 15) & ~15) + (((int64_t)20 * h->L.n_cap + 64 + 63) & ~(int64_t)63);
+    if (lds > 160 * 1024 || h->L.n_cap > 65535)
+      return sss_fail(-57, "sss_rollout_action: the LDS working set does not fit (simulator + Decima need " + std::to_string(lds) + " bytes for " + std::to_string(h->L.n_cap) +
+                               " node slots, a workgroup has " + std::to_string(160 * 1024) + ")");
+    d = sss_decima_device_args(g);
+    d.stage_idx = g->stage_idx_dev, d.num_exec = g->num_exec_dev, d.stage_sel = g->stage_sel_dev, d.job_idx = g->job_idx_dev, d.exec_sel = g->exec_sel_dev;
+    d.lgprob = g->lgprob_dev;
+  }
+  BeDeviceGuard guard(h->device);
+  const SssKernelArgs ka = sss_args(h);
+  if (int rc = wide ? sss_wide_launch_rollout_action(ka, h->L.num_envs, greedy != 0, policy_dev, param_dev, first_stage_in_dev, first_exec_in_dev, n_steps, steps_dev,
+                                                     first_stage_dev, first_exec_dev, g ? &d : nullptr, stream)
+                    : sss_narrow_launch_rollout_action(ka, h->L.num_envs, greedy != 0, policy_dev, param_dev, first_stage_in_dev, first_exec_in_dev, n_steps, steps_dev,
+                                                       first_stage_dev, first_exec_dev, g ? &d : nullptr, stream))
+    return sss_fail(-30, std::string("action rollout launch failed: ") + (rc < 0 ? "the LDS working set does not fit" : be_error(rc)));
+  return 0;
+}
+
 static int sss_decima_sample_any(int n_obs, int which, const sss_decima_sample_args* g, void* stream, bool argmax) {
   if (!g || n_obs < 1 || (which != 0 && which != 1)) return sss_fail(-1, "bad argument");
   if (g->num_executors < 1) return sss_fail(-28, "num_executors must be >= 1");

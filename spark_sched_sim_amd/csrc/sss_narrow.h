@@ -27,6 +27,11 @@ struct SssDecimaPolicyArgs;  // csrc/sss_decima_policy.h
 int sss_narrow_launch_rollout_decima(const SssKernelArgs& a, int num_envs, int greedy, const int32_t* policy_of, const int32_t* param_of, const int32_t* first_policy_of,
                                     const int32_t* first_param_of, int n_steps, int32_t* steps, int32_t* first_stage, int32_t* first_exec, const SssDecimaPolicyArgs& d,
                                     void* stream);
+// ... and the ones whose first step is a given action (csrc/sss_sim_action.h, likewise; d == nullptr: the heuristics' kernel, else the
+// Decima kernel, greedy: its arg-max form); no recording form. A negative return: the env layout's LDS working set does not fit
+int sss_narrow_launch_rollout_action(const SssKernelArgs& a, int num_envs, int greedy, const int32_t* policy_of, const int32_t* param_of, const int32_t* first_stage_in,
+                                    const int32_t* first_exec_in, int n_steps, int32_t* steps, int32_t* first_stage, int32_t* first_exec, const SssDecimaPolicyArgs* d,
+                                    void* stream);
 // ... and of the kernels that record the executor timelines (csrc/sss_hip_sim_tl.hip: the same unit compiled with -DSSS_TIMELINE;
 // the launchers above hand over to these when SssKernelArgs::tl is bound)
 int sss_narrow_tl_launch_reset(const SssKernelArgs& a, int num_envs, const uint64_t* seeds, const double* tl, const uint8_t* mask, void* stream);

@@ -800,4 +800,5 @@ SSS_KERNEL void SSS_KNAME(sss_rollout_heur_kernel)(SssKernelArgs a, int policy, 
 // (behind the #undefs: it brings in the GNN headers, whose names the short macros above must not touch)
 #ifndef SSS_TIMELINE
 #include "sss_sim_decima.h"  // ... and the one with Decima among the policies (sss_rollout_decima): the GNN inlined, kernels with a launch bound of their own
+#include "sss_sim_action.h"  // ... and the ones whose first step is a given action (sss_rollout_action), with and without Decima
 #endif

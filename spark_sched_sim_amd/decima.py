@@ -1070,6 +1070,82 @@ class DecimaPolicy(nn.Module):
                                                        o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), env._stream()))
         return out
 
+    def _env_policy_args(self, env, seed: int = 0, counter: int = 0, active8: torch.Tensor | None = None):
+        """the policy kernels' argument structure over this policy's packed weights and `env`'s work space (no score or profile outputs)"""
+        from .binding import SssDecimaPolicyArgs
+        if getattr(self, "_kb", None) is None:
+            self.bind_kernels(env._b)
+        assert self._use_kernels(), "the fused policy kernel supports the published Decima architecture only"
+        w, ws = self._packed_weights(), self._env_workspace(env)
+        return SssDecimaPolicyArgs(active8.data_ptr() if active8 is not None else None, 200.0, 1e5, self._packed[2],
+                                   w["prep"].data_ptr(), w["msg"].data_ptr(), w["update"].data_ptr(), w["dag"].data_ptr(), w["glob"].data_ptr(),
+                                   w["stage"].data_ptr(), w["exec"].data_ptr(), ws["node"].data_ptr(), ws["job"].data_ptr(),
+                                   int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), ws["stage_idx"].data_ptr(), ws["num_exec"].data_ptr(),
+                                   ws["stage_sel"].data_ptr(), ws["job_idx"].data_ptr(), ws["exec_sel"].data_ptr(), ws["lgprob"].data_ptr(), None, None, None)
+
+    @torch.no_grad()
+    def topk_env(self, env, k: int, active: torch.Tensor | None = None, out: dict[str, torch.Tensor] | None = None,
+                 want_scores: bool = False) -> dict[str, torch.Tensor]:
+        """the `k` best decisions of the arg-max policy for every env of a `VecSparkSchedSimEnv` in ONE kernel launch (include/sss.h
+        sss_decima_topk), asynchronous, nothing is read back. The encoder runs once per env; slot r holds the schedulable stage with
+        the r-th largest score (ties to the lower node index), in the env's action format, the arg-max executor count for that
+        stage's job and the policy's log-probability of the pair (one softmax over all schedulable stages, not over the slots). Slot
+        0 is `act_env(greedy=True)`'s decision bit for bit. Returns {"stage_idx", "num_exec" i32[B, k], "lgprob" f32[B, k], "count"
+        i32[B]}: `count` = max(1, min(k, schedulable stages)) slots are filled (with nothing schedulable slot 0 is the policy's
+        (-1, 1, 0.0)), the others hold (-1, -1, -inf); an env with `active == 0` gets count 0. `want_scores` (or an `out` that has the
+        key) adds "exec_scores" f32[B, k, E]: the count scores of each slot's job, -inf beyond its cap. `out`: such a dict from an
+        earlier call with the same k, written again. ValueError for k outside [1, 64]."""
+        import ctypes
+
+        from .vec_env import _mask_u8
+        B, dev, k = env.num_envs, env.device, int(k)
+        if not 1 <= k <= 64:
+            raise ValueError(f"topk_env: k must be in [1, 64], got {k}")
+        act8 = _mask_u8(active)  # (kept until the launch is queued)
+        a = self._env_policy_args(env, active8=act8)
+        if out is None:
+            out = {"stage_idx": torch.empty((B, k), dtype=torch.int32, device=dev), "num_exec": torch.empty((B, k), dtype=torch.int32, device=dev),
+                   "lgprob": torch.empty((B, k), dtype=torch.float32, device=dev), "count": torch.empty(B, dtype=torch.int32, device=dev)}
+            if want_scores:
+                out["exec_scores"] = torch.empty((B, k, self.num_executors), dtype=torch.float32, device=dev)
+        want = {"stage_idx": (torch.int32, B * k), "num_exec": (torch.int32, B * k), "lgprob": (torch.float32, B * k), "count": (torch.int32, B)}
+        if "exec_scores" in out:
+            want["exec_scores"] = (torch.float32, B * k * self.num_executors)
+        for name, (dt, n) in want.items():
+            t = out[name]
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"topk_env: out[{name!r}] must be a contiguous {dt} tensor of {n} entries on {dev}")
+        self._kb.check(self._kb.lib.sss_decima_topk(env._h, ctypes.byref(a), k, out["stage_idx"].data_ptr(), out["num_exec"].data_ptr(), out["lgprob"].data_ptr(),
+                                                    out["count"].data_ptr(), out["exec_scores"].data_ptr() if "exec_scores" in out else None, env._stream()))
+        return out
+
+    @torch.no_grad()
+    def rollout_action_env(self, env, n_steps: int, first_stage: torch.Tensor, first_exec: torch.Tensor, greedy: bool = True, seed: int = 0, counter: int = 0,
+                           policy: torch.Tensor | None = None, param: torch.Tensor | None = None,
+                           out: dict[str, torch.Tensor] | None = None) -> dict[str, torch.Tensor]:
+        """`rollout_env` whose first step is a given ACTION (include/sss.h sss_rollout_action), one asynchronous launch, nothing is read
+        back: where `first_exec[i] >= 1` env i first takes `(first_stage[i], first_exec[i])` verbatim, as `env.step` would, and then
+        up to `n_steps - 1` steps of its policy - Decima by default, `policy` / `param` as for `rollout_env`; `first_exec[i] == 0`
+        forces nothing; `first_exec[i] < 0` leaves env i untouched byte for byte (an empty `topk_env` slot can be handed over as it
+        is). The forced step is step 0 of the launch: a sampled follower's first decision draws with `counter + 1`. An action the env
+        refuses leaves the env's error as `env.step` does, ends the env's part and is not counted in `steps`. Returns `rollout_env`'s
+        dict. Refusals as `rollout_env`."""
+        import ctypes
+
+        B, dev = env.num_envs, env.device
+        if (policy is None) != (param is None):
+            raise ValueError("rollout_action_env: policy and param come together or not at all")
+        ptr = lambda t, what: env._i32_per_env(t, f"rollout_action_env: {what}").data_ptr() if t is not None else None  # noqa: E731
+        fs, fe = env._i32_per_env(first_stage, "rollout_action_env: first_stage"), env._i32_per_env(first_exec, "rollout_action_env: first_exec")
+        a = self._env_policy_args(env, seed, counter)
+        if out is None:
+            out = {"steps": torch.zeros(B, dtype=torch.int32, device=dev), "first_stage_idx": torch.full((B,), -1, dtype=torch.int32, device=dev),
+                   "first_num_exec": torch.zeros(B, dtype=torch.int32, device=dev)}
+        o = [env._i32_per_env(out[k], f"rollout_action_env: out[{k!r}]") for k in ("steps", "first_stage_idx", "first_num_exec")]
+        self._kb.check(self._kb.lib.sss_rollout_action(env._h, ctypes.byref(a), int(bool(greedy)), ptr(policy, "policy"), ptr(param, "param"), fs.data_ptr(),
+                                                       fe.data_ptr(), int(n_steps), o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), env._stream()))
+        return out
+
     @staticmethod
     def env_actions(a: dict[str, torch.Tensor]) -> dict[str, torch.Tensor]:
         """`act`'s result in the env's action format (DecimaActWrapper.action, env_wrapper.py:33-34);

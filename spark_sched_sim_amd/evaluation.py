@@ -190,7 +190,8 @@ def horizon_cost(t_arrival, t_completed, wall: float, t_stop: float, rem_work, n
 
 @torch.no_grad()
 def run_lookahead(env, scheduler, seed, *, q: Sequence[float] = (25, 50, 75, 100), check_every: int = DECISION_CHECK_EVERY) -> dict[str, torch.Tensor]:
-    """the parents of a `lookahead.LookaheadScheduler` on `env` play one whole episode under it: parents and children are reset
+    """the parents of a `lookahead.LookaheadScheduler` - or of a `lookahead.ActionLookaheadScheduler`, whose "candidates" are the top-k
+    slots - on `env` play one whole episode under it: parents and children are reset
     (`seed`: an int - parent number i gets seed + i - or one seed per parent; a child gets its parent's; no other env is touched by
     the reset), then `scheduler.decide_and_step()` until every parent's episode is over or `scheduler.max_steps` steps are played;
     the parents' done mask is read every `check_every` decisions (the one device->host sync). Returns the `run_episodes` dict with

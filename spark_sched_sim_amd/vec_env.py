@@ -383,6 +383,25 @@ class VecSparkSchedSimEnv:
                                                    self._stream()))
         return out
 
+    def rollout_action(self, policy: torch.Tensor, param: torch.Tensor, n_steps: int, first_stage: torch.Tensor, first_exec: torch.Tensor,
+                       out: dict[str, torch.Tensor] | None = None) -> dict[str, torch.Tensor]:
+        """`rollout_each` whose first step is a given ACTION (include/sss.h sss_rollout_action without policy arguments), one
+        asynchronous launch and no host sync: where `first_exec[i] >= 1` env i first takes `(first_stage[i], first_exec[i])` verbatim,
+        as `step` would, and then up to `n_steps - 1` steps under `policy[i]` / `param[i]`; `first_exec[i] == 0` forces nothing (the
+        policy decides every step); `first_exec[i] < 0` leaves env i untouched byte for byte, like `policy[i] == -1`. An action the env
+        refuses leaves the env's error as `step` does, ends the env's part and is not counted in `steps`. All four are int32 device
+        tensors [B]; nothing is read back. Returns `rollout_each`'s dict (`out`: such a dict to write again). The heuristics' ids only:
+        `DecimaPolicy.rollout_action_env` is the form with a Decima follower. Not available while a timeline is recorded (ValueError)."""
+        B, dev = self.num_envs, self.device
+        t = [self._i32_per_env(x, f"rollout_action: {what}") for x, what in ((policy, "policy"), (param, "param"), (first_stage, "first_stage"), (first_exec, "first_exec"))]
+        if out is None:
+            out = {"steps": torch.zeros(B, dtype=torch.int32, device=dev), "first_stage_idx": torch.full((B,), -1, dtype=torch.int32, device=dev),
+                   "first_num_exec": torch.zeros(B, dtype=torch.int32, device=dev)}
+        o = [self._i32_per_env(out[k], f"rollout_action: out[{k!r}]") for k in ("steps", "first_stage_idx", "first_num_exec")]
+        self._b.check(self._b.lib.sss_rollout_action(self._h, None, 0, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), int(n_steps),
+                                                     o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), self._stream()))
+        return out
+
     def lookahead_pick(self, parents: torch.Tensor, children: torch.Tensor, cand: dict[str, torch.Tensor], best: torch.Tensor, scores: torch.Tensor,
                        env_policy: dict[str, torch.Tensor]) -> None:
         """the decision of a lookahead from its finished children, one asynchronous launch (include/sss.h sss_lookahead_pick, where

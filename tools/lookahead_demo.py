@@ -5,9 +5,13 @@ which play to the end of the episode on the device. Prints each scheduler's cost
 time-average number of jobs in the system - with a 95 % confidence interval over the samples.
 
     python tools/lookahead_demo.py [--seed 0] [--at 150] [--samples 64] [--policies fair,fifo,sjfcp,wfair:1] [--horizon MS] [--tail srpt|none]
+                                    [--decima CHECKPOINT --topk K]
 
 With --horizon the children stop that span of simulated time after the fork (`continuations(fused=True, horizon=...)`); the figures
 describe the states they stopped in, and the cost the horizon lookahead would compare (`evaluation.horizon_cost`) is printed beside them.
+With --decima CHECKPOINT --topk K the Q-values of Decima's K best ACTIONS in that state are printed as well: slot r's children take
+the r-th best decision of the arg-max policy (`DecimaPolicy.topk_env`) and then follow Decima to the end of the episode
+(`DecimaPolicy.rollout_action_env`), each sample with its own task-duration noise - total job time, mean over the samples.
 """
 from __future__ import annotations
 
@@ -34,7 +38,11 @@ def main() -> None:
     ap.add_argument("--horizon", type=float, default=None, help="the children stop this span of simulated time after the fork")
     ap.add_argument("--tail", default="srpt", choices=("none", "srpt"))
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--decima", default=None, metavar="CHECKPOINT", help="a DecimaPolicy state dict (for --topk)")
+    ap.add_argument("--topk", type=int, default=0, help="with --decima: print the Q-values of Decima's K best actions from the state")
     args = ap.parse_args()
+    if args.topk and not args.decima:
+        ap.error("--topk needs --decima")
     policies = [(p.split(":")[0], int(p.split(":")[1]) if ":" in p else 0) for p in args.policies.split(",")]
     S = args.samples
     env = VecSparkSchedSimEnv(C1, 1 + S, device=args.device)
@@ -62,7 +70,39 @@ def main() -> None:
         ci = lambda v: float(1.96 * v.std() / max(n, 1) ** 0.5) if n > 1 else float("nan")  # noqa: E731
         print(f"{name + (':' + str(param) if param else ''):10s} mean job duration {float(dur.mean()):8.2f} +- {ci(dur):.2f} s   avg jobs in system {float(jobs.mean()):6.2f} +- {ci(jobs):.2f}   "
               f"({n} of {S} children finished)")
+    if args.topk:
+        action_values(env, args, children)
     env.close()
+
+
+def action_values(env, args, children) -> None:
+    """Q(state, a) for Decima's --topk best actions a, by Monte Carlo: `--samples // K` children per action, Decima (arg-max) behind it"""
+    from spark_sched_sim_amd.binding import POLICY_DECIMA
+    from spark_sched_sim_amd.decima import DecimaPolicy
+    agent = dict(embed_dim=16, gnn_mlp_kwargs=dict(hid_dims=[32, 16], act_cls="LeakyReLU", act_kwargs=dict(negative_slope=0.2)),
+                 policy_mlp_kwargs=dict(hid_dims=[64, 64], act_cls="Tanh"))
+    policy = DecimaPolicy(num_executors=C1["num_executors"], **agent, state_dict_path=args.decima).to(env.device).eval()
+    B, K = env.num_envs, args.topk
+    per = max(1, len(children) // K)
+    kids = torch.tensor(children[: per * K], dtype=torch.long, device=env.device).reshape(K, per)
+    env.fork([0] * (per * K), children[: per * K], reseed=[1000 + k % per for k in range(per * K)])  # (sample s of every action draws the same noise)
+    active = torch.zeros(B, dtype=torch.bool, device=env.device)
+    active[0] = True
+    top = policy.topk_env(env, K, active=active)
+    pol = torch.full((B,), -1, dtype=torch.int32, device=env.device)
+    stage, nexec = torch.full_like(pol, -1), torch.full_like(pol, -1)
+    pol[kids.reshape(-1)] = POLICY_DECIMA
+    stage[kids.reshape(-1)] = top["stage_idx"][0][:, None].expand(K, per).reshape(-1)
+    nexec[kids.reshape(-1)] = top["num_exec"][0][:, None].expand(K, per).reshape(-1)
+    policy.rollout_action_env(env, 200_000, stage, nexec, greedy=True, policy=pol, param=torch.zeros_like(pol))
+    cost = env.job_stats()["stats"][:, 1]
+    ok = (env.header_field("terminated") != 0) & (env.obs_i32[:, 7] == 0)
+    print(f"Decima's {int(top['count'][0])} best actions of {K} asked for (total job time to the episode's end, {per} samples each, Decima behind the action):")
+    for r in range(int(top["count"][0])):
+        c = cost[kids[r]][ok[kids[r]]]
+        ci = float(1.96 * c.std() / c.numel() ** 0.5) if c.numel() > 1 else float("nan")
+        print(f"  slot {r}: stage_idx {int(top['stage_idx'][0, r]):3d} num_exec {int(top['num_exec'][0, r]):3d} log-prob {float(top['lgprob'][0, r]):8.3f}   "
+              f"Q = {float(c.mean()) if c.numel() else float('nan'):14.1f} +- {ci:.1f}   ({c.numel()} of {per} children finished)")
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@ children, the pick kernel, a step of the parents - four launches per decision), 
 
     python tools/lookahead_eval.py [--envs 256] [--samples 1] [--reseed N] [--replan-every 1] [--base name[:param]]
                                    [--policies fair,fifo,sjfcp,wfair:1] [--chunk 64] [--horizon MS[,MS...]] [--tail srpt|none] [--no-full]
-                                   [--decima CHECKPOINT]
+                                   [--decima CHECKPOINT] [--topk K[,K...]]
 
 Without --reseed the children continue the parent's own future (exact lookahead: never above a candidate's own episode); with it
 every sample draws its own task durations (Monte-Carlo lookahead: what a scheduler that does not know the future can do).
@@ -16,6 +16,8 @@ to the best candidate and to SJF-CP, the children's steps per decision (mean and
 With --decima CHECKPOINT (a state dict of `DecimaPolicy`, the reference's models/decima/model.pt as it is) the learned policy's arg-max
 decisions are one more candidate, "decima" - it may also be the --base - and one more column: its own episodes (`run_episodes(...,
 fused=True)`). Not together with --horizon.
+With --topk 2,4 (needs --decima) every listed K gets one more run, "topK": the lookahead over Decima's K best ACTIONS with Decima as the
+base policy (`lookahead.ActionLookaheadScheduler`; --samples, --reseed and --replan-every apply), on the same sequences.
 The parents are handled `--chunk` at a time: a chunk needs chunk * (1 + candidates * samples) env slots."""
 from __future__ import annotations
 
@@ -31,7 +33,7 @@ ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from spark_sched_sim_amd import VecSparkSchedSimEnv, evaluation  # noqa: E402
-from spark_sched_sim_amd.lookahead import LookaheadScheduler  # noqa: E402
+from spark_sched_sim_amd.lookahead import ActionLookaheadScheduler, LookaheadScheduler  # noqa: E402
 
 C1 = dict(num_executors=10, job_arrival_cap=50, job_arrival_rate=4.0e-5, moving_delay=2000.0, warmup_delay=1000.0)
 TENSOR_KEYS = ("ok", "steps", "avg_num_jobs", "avg_job_duration_s", "episode_avg_job_duration_s", "total_job_time", "pct", "sorted")
@@ -45,7 +47,7 @@ def label(p: tuple[str, int]) -> str:
     return p[0] + (f":{p[1]}" if p[1] else "")
 
 
-class CountingScheduler(LookaheadScheduler):
+class _Counting:
     """counts the children's steps on the device (no sync): their sum and the longest child over all decisions"""
 
     def reset(self) -> None:
@@ -58,6 +60,14 @@ class CountingScheduler(LookaheadScheduler):
         steps = self.child_out["steps"][self._fork_dst.long()].clamp(min=0)
         self.child_steps += steps.sum()
         self.longest_child = torch.maximum(self.longest_child, steps.max())
+
+
+class CountingScheduler(_Counting, LookaheadScheduler):
+    pass
+
+
+class CountingActionScheduler(_Counting, ActionLookaheadScheduler):
+    pass
 
 
 def main() -> None:
@@ -77,7 +87,11 @@ def main() -> None:
     ap.add_argument("--no-full", action="store_true", help="with --horizon: leave the full-episode lookahead out")
     ap.add_argument("--tag", default=None, help="key of this run in the output file (default: made of the flags); other keys are kept")
     ap.add_argument("--decima", default=None, metavar="CHECKPOINT", help="a DecimaPolicy state dict: Decima (arg-max) as a candidate and a column of its own")
+    ap.add_argument("--topk", default=None, metavar="K[,K...]", help="with --decima: one more run per K, the lookahead over Decima's K best actions (base Decima)")
     args = ap.parse_args()
+    topk = [int(k) for k in args.topk.split(",")] if args.topk else []
+    if topk and not args.decima:
+        ap.error("--topk needs --decima")
     cands = [parse_policy(p) for p in args.policies.split(",")]
     args.policy = None
     if args.decima:
@@ -102,6 +116,10 @@ def main() -> None:
     for horizon in ([] if horizons and args.no_full else [None]) + horizons:
         runs["lookahead" if horizon is None else f"H{horizon:g}"] = run_lookaheads(env, args, cands, base, seeds, chunk, horizon)
     env.close()
+    for k in topk:
+        env = VecSparkSchedSimEnv(C1, chunk * (1 + k * S), device=args.device)
+        runs[f"top{k}"] = run_lookaheads(env, args, cands, base, seeds, chunk, None, topk=k)
+        env.close()
     for name, (res, _) in runs.items():
         results[name] = res
 
@@ -138,14 +156,19 @@ def main() -> None:
     print(f"  envs compared {table['envs_compared']}")
 
 
-def run_lookaheads(env, args, cands, base, seeds, chunk: int, horizon) -> tuple[dict, dict]:
-    """the lookahead's episodes on all `seeds`, `chunk` parents at a time -> (the `run_episodes` dict, the run's figures)"""
-    N, K, S = len(seeds), len(cands), args.samples
+def run_lookaheads(env, args, cands, base, seeds, chunk: int, horizon, topk: int | None = None) -> tuple[dict, dict]:
+    """the lookahead's episodes on all `seeds`, `chunk` parents at a time -> (the `run_episodes` dict, the run's figures). `topk`: the
+    lookahead over Decima's `topk` best actions instead of the one over `cands`"""
+    N, K, S = len(seeds), topk or len(cands), args.samples
     parts, decisions, fallbacks, wall, child_steps, longest = [], 0, 0, 0.0, 0, 0
     for at in range(0, N, chunk):
         n = min(chunk, N - at)
-        sched = CountingScheduler(env, list(range(n)), cands, base=base, samples=S, reseed=args.reseed, replan_every=args.replan_every,
-                                  children=list(range(chunk, chunk + n * K * S)), horizon=horizon, tail=args.tail, decima=args.policy)
+        if topk:
+            sched = CountingActionScheduler(env, list(range(n)), args.policy, topk, samples=S, reseed=args.reseed, replan_every=args.replan_every,
+                                            children=list(range(chunk, chunk + n * K * S)))
+        else:
+            sched = CountingScheduler(env, list(range(n)), cands, base=base, samples=S, reseed=args.reseed, replan_every=args.replan_every,
+                                      children=list(range(chunk, chunk + n * K * S)), horizon=horizon, tail=args.tail, decima=args.policy)
         if env.device.type == "cuda":
             torch.cuda.synchronize(env.device)
         t0 = time.perf_counter()
@@ -165,7 +188,8 @@ def run_lookaheads(env, args, cands, base, seeds, chunk: int, horizon) -> tuple[
     # (children of a parent that is over take no step: the mean is over the decisions of parents that were still playing)
     stats = {"horizon": horizon, "decisions": decisions, "fallbacks": fallbacks, "lookahead_wall_s": wall, "decisions_per_s": decisions / wall if wall > 0 else None,
              "child_steps_mean": child_steps / max(decisions * K * S, 1), "child_steps_longest": longest,
-             "winner_share": {label(c): float((winners == k).double().mean()) for k, c in enumerate(cands)} if winners.numel() else {}}
+             "winner_share": {f"slot{k}" if topk else label(c): float((winners == k).double().mean())
+                              for k, c in enumerate(range(topk) if topk else cands)} if winners.numel() else {}}
     return res, stats
 
 
