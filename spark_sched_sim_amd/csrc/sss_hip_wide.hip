@@ -41,6 +41,11 @@ int SSS_LAUNCHER(step)(const SssKernelArgs& a, int num_envs, const int32_t* stag
 }
 #ifndef SSS_TIMELINE
 int SSS_LAUNCHER(policy)(const SssKernelArgs& a, int num_envs, int policy, int param, int32_t* stage_idx, int32_t* num_exec, void* stream) {
+  if (policy == SSS_POLICY_HASH) {  // a thread per env, nothing staged (sss_sim.h)
+    hipLaunchKernelGGL(SSS_KNAME(sss_policy_hash_kernel), dim3((num_envs + SSS_POLICY_HASH_THREADS - 1) / SSS_POLICY_HASH_THREADS), dim3(SSS_POLICY_HASH_THREADS), 0,
+                       (hipStream_t)stream, a, num_envs, param, stage_idx, num_exec);
+    return (int)hipGetLastError();
+  }
   hipLaunchKernelGGL(SSS_KNAME(sss_policy_kernel), dim3(num_envs), dim3(64), (size_t)a.P.pool_bytes, (hipStream_t)stream, a, policy, param, stage_idx, num_exec);
   return (int)hipGetLastError();
 }

@@ -311,6 +311,15 @@ SSS_DEV int pool_index(uint32_t k) {
   if (s < 0) return 1 + j;
   return 1 + g_c.J_cap + j * g_c.SP + s;
 }
+// The same rule with the env's dimensions handed in (policy_hash_direct: a lane whose env is not the wave's). Written out a second
+// time: with pool_index calling this one, the reset and fused rollout kernels came out with another register allocation
+// (profiles/policy_hash_launch.md section 4), and tests/test_abi.py holds theirs.
+SSS_DEV int pool_index_in(uint32_t k, int J_cap, int SP) {
+  int j = key_job(k), s = key_stage(k);
+  if (j < 0) return 0;
+  if (s < 0) return 1 + j;
+  return 1 + J_cap + j * SP + s;
+}
 
 // job.local_executors (JOB:81-89) is only ever counted (TPCH:217, the executor-level key). Up to 64 executors it is kept as a
 // bit mask (the event batches update it with lane masks); the wide instantiation keeps the count itself in the same field.
@@ -700,12 +709,11 @@ SSS_DEV uint64_t splitmix64(uint64_t x) {
 // the build's counter-based uniform-random policy, keyed (episode seed, step in episode); mirrors
 // hash_policy in tests/golden/make_golden.py. SURVEY 8(d) C2: stage uniform over the schedulable
 // stages, num_exec uniform in [1, num_committable]; `p_none_permille` adds stage_idx = -1 draws.
-SSS_DEV void policy_hash(int p_none_permille, int& stage_idx, int& num_exec) {
-  uint64_t seed = g_hot.h.seed;
-  uint64_t step = (uint64_t)g_hot.h.ep_steps;
-  int n_sched = g_hot.h.n_sched;
-  int ncommit = obs_num_committable();
-  wave_sync();  // reads above vs. lane 0's writes in the step that follows
+// The policy is two parts. hash_action is the pure mapping from what the policy sees of an env to its action - the one
+// definition of the arithmetic; the two functions after it only differ in where they fetch those inputs from. (`step` is the
+// header's ep_steps, widened by the caller: policy_hash widens it where it always has, ahead of its ordering point, and the fused
+// rollout kernels keep their code, scalar spills included - profiles/policy_hash_launch.md section 4.)
+SSS_DEV void hash_action(uint64_t seed, uint64_t step, int n_sched, int ncommit, int p_none_permille, int& stage_idx, int& num_exec) {
   uint64_t h = splitmix64((seed << 32) ^ step), h2 = splitmix64(h), h3 = splitmix64(h2);
   if (n_sched == 0 || (int)(h3 % 1000) < p_none_permille)
     stage_idx = -1;
@@ -713,8 +721,37 @@ SSS_DEV void policy_hash(int p_none_permille, int& stage_idx, int& num_exec) {
     stage_idx = (int)(h % (uint64_t)n_sched);
   num_exec = 1 + (int)(h2 % (uint64_t)(ncommit > 0 ? ncommit : 1));
 }
+// ... from the env the wave has staged (the header in LDS, the pool records through g_c): the fused rollout kernels
+SSS_DEV void policy_hash(int p_none_permille, int& stage_idx, int& num_exec) {
+  uint64_t seed = g_hot.h.seed;
+  uint64_t step = (uint64_t)g_hot.h.ep_steps;
+  int n_sched = g_hot.h.n_sched;
+  int ncommit = obs_num_committable();
+  wave_sync();  // reads above vs. lane 0's writes in the step that follows
+  hash_action(seed, step, n_sched, ncommit, p_none_permille, stage_idx, num_exec);
+}
+// ... from the HBM image of env `env`, by one lane that stages nothing: two dependent loads (four header words, then the source
+// pool's record - none when there is no source), no LDS, no collective. The env's regions are found through the layout in `a`,
+// not through g_c, which describes the one env of a wave: here every lane may have an env of its own (sss_policy_hash_kernel).
+SSS_DEV void policy_hash_direct(const SssKernelArgs& a, int env, int p_none_permille, int& stage_idx, int& num_exec) {
+  const uint8_t* base = (const uint8_t*)a.B.state + (size_t)env * (size_t)a.L.env_stride;
+  const auto* hd = SSS_AS_HBM(SssHdr, base);  // (the hot block, header first, opens the env's image)
+  const uint64_t seed = hd->seed;
+  const uint64_t step = (uint64_t)hd->ep_steps;
+  const int n_sched = hd->n_sched;
+  const uint32_t srck = hd->curr_source;
+  int ncommit = 0;
+  if (srck != POOL_NONE) {
+    // of the pool's 16-byte record the word that holds used | commit_from << 16, as the observation writer reads it
+    const auto* rec = SSS_AS_HBM(SssPoolHdr, base + a.L.off_pool_hdr) + pool_index_in(srck, a.L.J_cap, a.L.SP);
+    const uint32_t used_cf = *SSS_AS_HBM(uint32_t, &rec->used);
+    ncommit = (int)(uint16_t)used_cf - (int)(int16_t)(used_cf >> 16);
+  }
+  hash_action(seed, step, n_sched, ncommit, p_none_permille, stage_idx, num_exec);
+}
 
 enum { SSS_POLICY_FAIR = 0, SSS_POLICY_FIFO = 1, SSS_POLICY_HASH = 2, SSS_POLICY_WFAIR = 3, SSS_POLICY_SJFCP = 4 };
+#define SSS_POLICY_HASH_THREADS 256  // envs per workgroup of sss_policy_hash_kernel (below; its launchers: sss_hip_sim.hip, sss_hip_wide.hip)
 
 // kHeuristics: with weighted fair / SJF-CP (ids 3, 4). Without them the code is fair / FIFO / hash only, so that the rollout
 // kernel those run in keeps its register allocation (see sss_rollout_heur_kernel)
@@ -735,13 +772,32 @@ SSS_DEV void run_policy(int policy, int param, int& stage_idx, int& num_exec) {
 #ifndef SSS_TIMELINE  // (reads the state only: there is no recording form of it)
 SSS_KERNEL void SSS_KNAME(sss_policy_kernel)(SssKernelArgs a, int policy, int param, int32_t* stage_idx, int32_t* num_exec) {
   int env = wave_env();
-  uint8_t* base = (uint8_t*)a.B.state + (size_t)env * a.L.env_stride;
-  ctx_init();
-  env_begin_readonly(base);
   int si, ne;
-  run_policy(policy, param, si, ne);
+  if (policy == SSS_POLICY_HASH) {
+    // The hash policy needs nothing staged. The launchers of the gfx950 build send it to sss_policy_hash_kernel below and never
+    // get here; the CPU emulator launches this kernel for every policy and so runs the same loads, on every lane of the wave.
+    policy_hash_direct(a, env, param, si, ne);
+  } else {
+    uint8_t* base = (uint8_t*)a.B.state + (size_t)env * a.L.env_stride;
+    ctx_init();
+    env_begin_readonly(base);
+    run_policy(policy, param, si, ne);
+  }
   if (wave_lane() == 0) stage_idx[env] = si, num_exec[env] = ne;
 }
+// The hash policy with a thread per env: a workgroup per env above means 4096 dispatches, each staging the header, the slot
+// map and the active-job list, for four header words and one pool record. Here 256 envs share a workgroup, nothing is staged
+// and no LDS is asked for. (No emulator form: there a "kernel" is a wave with one env.)
+#ifdef __HIP__
+extern "C" __global__ __launch_bounds__(SSS_POLICY_HASH_THREADS) void SSS_KNAME(sss_policy_hash_kernel)(SssKernelArgs a, int num_envs, int param, int32_t* stage_idx,
+                                                                                                     int32_t* num_exec) {
+  const int env = (int)(blockIdx.x * SSS_POLICY_HASH_THREADS + threadIdx.x);
+  if (env >= num_envs) return;
+  int si, ne;
+  policy_hash_direct(a, env, param, si, ne);
+  stage_idx[env] = si, num_exec[env] = ne;
+}
+#endif
 #endif
 
 // n_steps x (policy -> step -> observe) per env in one launch; the env's hot block and job cache
